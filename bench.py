@@ -6,7 +6,16 @@ One "step" = one complete breadth-first check of TwoPhaseSys{rms: 0..9} (10 340 
 allocator caches the visited set and frontiers across steps; the per-step memset of the visited
 set is inside the timed region).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`); nothing else runs. `--full` adds the side measurements to the line: the roofline and
+counting passes, `levels`, `no_hint`, `config4`, `replicas` (N > 1) and `cpu_baseline` (N = 1).
+`--dump-outputs DIR` writes what the last timed check returned to its caller as DIR/<name>.npy
+(float64): `counts` = [unique_state_count, state_count, max_depth] and `discovery_lengths` = per
+property, in `properties()` order, the length of its discovery path (-1: none). Both are the same in
+every visit order of a complete check, so two builds can be compared file for file (the discovery
+paths themselves are not written: FAST order may find another shortest path from run to run).
 
 N > 1: one process per GPU. If WORLD_SIZE is not set, this script starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a CHILD process (before
@@ -28,8 +37,8 @@ it was compiled against) is the only GPU runtime in the process; ranks bootstrap
 launcher's environment (stateright_amd.distributed.Communicator.from_env) and the timing barrier /
 max-over-ranks are the engine's own (sr_dist_barrier, sr_dist_allreduce_f64).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the expand kernel, HIP-event
-timed on the engine's stream) and, at N=1, `cpu_baseline` (the CPU restatement of the reference
+Prints ONE JSON line on rank 0; with `--full` it carries `roofline` (dominant kernel = the expand
+kernel, HIP-event timed on the engine's stream) and, at N=1, `cpu_baseline` (the CPU restatement of the reference
 `spawn_bfs`, oracle/bfs_cli, on the same 2pc N=9 check, host threads and 1 thread).
 """
 import argparse
@@ -77,6 +86,12 @@ def parse():
     ap.add_argument("--clients", type=int, default=3, help="paxos / single_copy client_count")
     ap.add_argument("--threads", type=int, default=10, help="increment_lock thread count")
     ap.add_argument("--order", default="fast", choices=["fast", "fifo"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements (roofline and counting passes, "
+                         "`no_hint`, `config4`, `replicas`, `cpu_baseline`); the options below that size them "
+                         "apply only then")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed check returned (counts, discovery path lengths) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU restatement (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads for the CPU baseline (0 = usable CPUs)")
     ap.add_argument("--no-hint-steps", type=int, default=10,
@@ -386,12 +401,102 @@ def main():
         c = None
         c = step()
         unique += c.unique_state_count()
+    # What the last timed check returned is read before it is freed; the reading belongs to no step
+    # and is taken out of the timed region. (Deferred discovery paths of a partitioned check are
+    # built collectively: every rank asks, in the same order.)
+    t_read = time.perf_counter()
+    st = c.stats()
+    final_state_count = c.state_count()
+    outputs = None
+    if args.dump_outputs:
+        outputs = {"counts": [c.unique_state_count(), final_state_count, c.max_depth()],
+                   "discovery_lengths": [-1 if p is None else len(p)
+                                         for p in (c.discovery(name) for name, _ in c.properties())]}
+    t_read = time.perf_counter() - t_read
     # the last checker is freed inside the timed region too: a freed checker's visited set is
     # cleared on the device behind it (the next check takes it clean), so every step pays its clear
     c = None
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - t_read
+    if world > 1:
+        elapsed = comm.allreduce([elapsed], "max")[0]
+    if outputs is not None and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, values in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(values, dtype=np.float64))
 
+    unique_total = float(unique) if partitioned or world == 1 else float(unique) * world
+
+    # --full: the side measurements, after the headline's timed region.
+    passes = no_hint = config4 = replicas = None
+    if args.full:
+        passes = roofline_passes(args, step, barrier, partitioned)
+        st, final_state_count = passes["st"], passes["final_state_count"]
+        if args.no_hint_steps > 0:
+            no_hint = measure_no_hint(args, world, comm, step, barrier, partitioned, expect_unique)
+        if args.config4_steps > 0 and args.model == "2pc":
+            config4 = measure_config4(args, world, comm, dev, barrier)
+        # (SR_BENCH_REPLICAS=1 runs it at N=1 in --mode rccl1 too: the rehearsal of this code path)
+        if partitioned and (world > 1 or os.environ.get("SR_BENCH_REPLICAS") == "1"):
+            replicas = measure_replicas(args, world, comm, dev, make, expect_unique, label, barrier)
+
+    if rank != 0:
+        comm.close()
+        return
+
+    res = {
+        "metric": "unique states/sec (whole node) + HBM GB/s, 2pc N=9 at 1/2/4/8 MI355X",
+        "value": unique_total / elapsed,
+        "unit": "unique states/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if (world == 1 or partitioned) else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": f"synthetic: the {args.model} model's own state space (no dataset)",
+        "config": {
+            "workload": f"{label} spawn_bfs, full check per step ({expect_unique} unique states)",
+            "model": args.model,
+            "rm_count": n if args.model == "2pc" else None,
+            "order": "fast" if partitioned else args.order,
+            "parallelism": (f"partitioned{world} ({exchange_label(st)})" if partitioned else
+                            f"replicas{world}" if world > 1 else "1 GPU"),
+            "world_size": world,
+            "comm": comm.kind() if comm is not None else None,
+            "rccl_nranks": comm.nranks() if comm is not None else None,
+        },
+        "state_count_per_sec": float(final_state_count) * (1 if partitioned else world) * args.steps / elapsed,
+    }
+    if passes is not None:
+        res["roofline"], res["levels"] = roofline_fields(args, world, partitioned, label, passes)
+    res["engine"] = {k: st[k] for k in ("levels", "table_capacity", "rehashes", "level_loop_sec", "total_sec",
+                                        "restarts", "pipelined", "records_routed", "head_levels")}
+    res["runtime"] = {"hip": versions["hip"], "rccl": versions["rccl"], "libs": N.loaded_runtime_paths(),
+                      "lib_digest": N.build_digest(),
+                      "source_digest": __import__("stateright_amd.build").build.source_digest()}
+    if no_hint is not None:
+        no_hint["vs_value"] = no_hint["value"] / res["value"]
+        res["no_hint"] = no_hint
+    if config4 is not None:
+        res["config4"] = config4
+    if replicas is not None:
+        res["replicas"] = replicas
+    if args.full and args.cpu_baseline and world == 1:
+        try:
+            res["cpu_baseline"] = cpu_baseline(args, n)
+        except Exception as e:  # the GPU number stands on its own
+            res["cpu_baseline"] = {"error": str(e)}
+    print(json.dumps(res), flush=True)
+    if comm is not None:
+        comm.close()
+
+
+def roofline_passes(args, step, barrier, partitioned):
+    """--full: the two measurement passes behind `roofline` and `levels`, K checks each."""
     # Roofline pass: the same K checks again with HIP events around every expand launch, on the
     # engine's own stream; achieved bytes / summed event time of the dominant kernel.
     kernel_ms = 0.0
@@ -427,44 +532,38 @@ def main():
         cas += stc["cas"]
         per_launch = cc.launch_counters() if not partitioned else []
         cc = None
+    return {"kernel_ms": kernel_ms, "launches": launches, "alg_bytes": alg_bytes, "st": st, "prof": prof,
+            "final_state_count": final_state_count, "probes": probes, "cas": cas, "per_launch": per_launch,
+            "profiled_elapsed": profiled_elapsed}
+
+
+def measure_no_hint(args, world, comm, step, barrier, partitioned, expect_unique):
+    """The path users get: the same checks without capacity_hint (the visited set and the arena grow
+    during the check, as the reference's DashMap does). Not `value`: reported beside it."""
+    step(hint=False)  # warmup
+    barrier()
+    t2 = time.perf_counter()
+    c = None
+    for _ in range(args.no_hint_steps):
+        c = None
+        c = step(hint=False)
+    stn = c.stats()
+    c = None
+    barrier()
+    el_nh = time.perf_counter() - t2
     if world > 1:
-        elapsed = comm.allreduce([elapsed], "max")[0]
-    unique_total = float(unique) if partitioned or world == 1 else float(unique) * world
+        el_nh = comm.allreduce([el_nh], "max")[0]
+    nh_total = expect_unique * args.no_hint_steps * (1 if partitioned or world == 1 else world)
+    return {"steps": args.no_hint_steps, "ms_per_step": el_nh / args.no_hint_steps * 1e3,
+            "value": nh_total / el_nh, "unit": "unique states/s",
+            "rehashes": stn["rehashes"], "table_capacity": stn["table_capacity"], "restarts": stn["restarts"]}
 
-    # The path users get: the same checks without capacity_hint (the visited set and the arena grow
-    # during the check, as the reference's DashMap does). Not `value`: reported beside it.
-    no_hint = None
-    if args.no_hint_steps > 0:
-        step(hint=False)  # warmup
-        barrier()
-        t2 = time.perf_counter()
-        c = None
-        for _ in range(args.no_hint_steps):
-            c = None
-            c = step(hint=False)
-        stn = c.stats()
-        c = None
-        barrier()
-        el_nh = time.perf_counter() - t2
-        if world > 1:
-            el_nh = comm.allreduce([el_nh], "max")[0]
-        nh_total = expect_unique * args.no_hint_steps * (1 if partitioned or world == 1 else world)
-        no_hint = {"steps": args.no_hint_steps, "ms_per_step": el_nh / args.no_hint_steps * 1e3,
-                   "value": nh_total / el_nh, "unit": "unique states/s",
-                   "rehashes": stn["rehashes"], "table_capacity": stn["table_capacity"], "restarts": stn["restarts"]}
 
-    config4 = None
-    if args.config4_steps > 0 and args.model == "2pc":
-        config4 = measure_config4(args, world, comm, dev, barrier)
-    replicas = None
-    # (SR_BENCH_REPLICAS=1 runs it at N=1 in --mode rccl1 too: the rehearsal of this code path)
-    if partitioned and (world > 1 or os.environ.get("SR_BENCH_REPLICAS") == "1"):
-        replicas = measure_replicas(args, world, comm, dev, make, expect_unique, label, barrier)
-
-    if rank != 0:
-        comm.close()
-        return
-
+def roofline_fields(args, world, partitioned, label, passes):
+    """The result line's `roofline` and `levels` from the passes of `roofline_passes`."""
+    kernel_ms, launches, alg_bytes, st = passes["kernel_ms"], passes["launches"], passes["alg_bytes"], passes["st"]
+    prof, per_launch, probes, cas = passes["prof"], passes["per_launch"], passes["probes"], passes["cas"]
+    profiled_elapsed = passes["profiled_elapsed"]
     avg_launch_ms = kernel_ms / max(1, launches)
     if partitioned:
         alg_bytes /= world  # this rank's share of the check's algorithmic bytes
@@ -504,95 +603,51 @@ def main():
     big = sum(ms for ms, _ in prof if ms >= BIG_LEVEL_MS)
     small = sum(ms for ms, _ in prof if ms < BIG_LEVEL_MS)
     span_ms = st["level_loop_sec"] * 1e3
-    res = {
-        "metric": "unique states/sec (whole node) + HBM GB/s, 2pc N=9 at 1/2/4/8 MI355X",
-        "value": unique_total / elapsed,
-        "unit": "unique states/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if (world == 1 or partitioned) else "weak",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": f"synthetic: the {args.model} model's own state space (no dataset)",
-        "config": {
-            "workload": f"{label} spawn_bfs, full check per step ({expect_unique} unique states)",
-            "model": args.model,
-            "rm_count": n if args.model == "2pc" else None,
-            "order": "fast" if partitioned else args.order,
-            "parallelism": (f"partitioned{world} ({exchange_label(st)})" if partitioned else
-                            f"replicas{world}" if world > 1 else "1 GPU"),
-            "world_size": world,
-            "comm": comm.kind() if comm is not None else None,
-            "rccl_nranks": comm.nranks() if comm is not None else None,
-        },
-        "state_count_per_sec": float(final_state_count) * (1 if partitioned else world) * args.steps / elapsed,
-        "roofline": {
-            # HBM-side: random visited-set probes and claims (8-byte accesses that each move a
-            # memory line) and streamed frontiers. `limiter` names the largest fraction of a bound
-            # the kernel cannot exceed.
-            "bound": "hbm",
-            "limiter": max(fracs, key=fracs.get),
-            "fractions": fracs,
-            "kernel": ("expand_route" if partitioned else "expand_fast") +
-                      " (expand + fingerprint + visited-set probe/claim + append + properties)",
-            "achieved": achieved_gbps,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": achieved_gbps / HBM_PEAK_GBPS,
-            "traffic": traffic,
-            "traffic_gbps": traffic / launch_s / 1e9 if traffic and launch_s else None,
-            "memory_side_requests": ea,
-            "pmc": pmc_note,
-            # context: visited-set probes and claims per second of kernel time (device counters)
-            # beside the uniform random-access rates of one 256 MiB table
-            "probe_rate": probe_rate,
-            "cas_rate": cas_rate,
-            "uniform_load_rate": UNIFORM_LOAD_RATE,
-            "uniform_cas_rate": UNIFORM_CAS_RATE,
-            "probes_per_step": probes / args.steps,
-            "big_levels": big_rate,
-            "avg_launch_ms": avg_launch_ms,
-            "launches_per_step": launches / args.steps,
-            "algorithmic_bytes_per_step": alg_bytes / args.steps,
-            "profiled_ms_per_step": profiled_elapsed / args.steps * 1e3,
-        },
-        "levels": {
-            "span_ms": span_ms,
-            "big_levels_ms": big,
-            "big_levels": sum(1 for ms, _ in prof if ms >= BIG_LEVEL_MS),
-            "small_levels_ms": small,
-            "small_levels": sum(1 for ms, _ in prof if ms < BIG_LEVEL_MS),
-            "gaps_ms": max(0.0, span_ms - big - small) if prof else None,
-            "kernel_us": [round(ms * 1e3, 1) for ms, _ in prof],
-            "frontier": [fr for _, fr in prof],
-            # visited-set loads and CAS claims of each launch (counting pass): DESIGN.md §3's
-            # attribution of the level times
-            "probes": [int(p) for p, _ in per_launch] if len(per_launch) == len(prof) else None,
-            "cas": [int(c) for _, c in per_launch] if len(per_launch) == len(prof) else None,
-        } if prof else None,
-        "engine": {k: st[k] for k in ("levels", "table_capacity", "rehashes", "level_loop_sec", "total_sec",
-                                      "restarts", "pipelined", "records_routed", "head_levels")},
-        "runtime": {"hip": versions["hip"], "rccl": versions["rccl"], "libs": N.loaded_runtime_paths(),
-                    "lib_digest": N.build_digest(), "source_digest": __import__("stateright_amd.build").build.source_digest()},
+    roofline = {
+        # HBM-side: random visited-set probes and claims (8-byte accesses that each move a
+        # memory line) and streamed frontiers. `limiter` names the largest fraction of a bound
+        # the kernel cannot exceed.
+        "bound": "hbm",
+        "limiter": max(fracs, key=fracs.get),
+        "fractions": fracs,
+        "kernel": ("expand_route" if partitioned else "expand_fast") +
+                  " (expand + fingerprint + visited-set probe/claim + append + properties)",
+        "achieved": achieved_gbps,
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": achieved_gbps / HBM_PEAK_GBPS,
+        "traffic": traffic,
+        "traffic_gbps": traffic / launch_s / 1e9 if traffic and launch_s else None,
+        "memory_side_requests": ea,
+        "pmc": pmc_note,
+        # context: visited-set probes and claims per second of kernel time (device counters)
+        # beside the uniform random-access rates of one 256 MiB table
+        "probe_rate": probe_rate,
+        "cas_rate": cas_rate,
+        "uniform_load_rate": UNIFORM_LOAD_RATE,
+        "uniform_cas_rate": UNIFORM_CAS_RATE,
+        "probes_per_step": probes / args.steps,
+        "big_levels": big_rate,
+        "avg_launch_ms": avg_launch_ms,
+        "launches_per_step": launches / args.steps,
+        "algorithmic_bytes_per_step": alg_bytes / args.steps,
+        "profiled_ms_per_step": profiled_elapsed / args.steps * 1e3,
     }
-    if no_hint is not None:
-        no_hint["vs_value"] = no_hint["value"] / res["value"]
-        res["no_hint"] = no_hint
-    if config4 is not None:
-        res["config4"] = config4
-    if replicas is not None:
-        res["replicas"] = replicas
-    if args.cpu_baseline and world == 1:
-        try:
-            res["cpu_baseline"] = cpu_baseline(args, n)
-        except Exception as e:  # the GPU number stands on its own
-            res["cpu_baseline"] = {"error": str(e)}
-    print(json.dumps(res), flush=True)
-    if comm is not None:
-        comm.close()
+    levels = {
+        "span_ms": span_ms,
+        "big_levels_ms": big,
+        "big_levels": sum(1 for ms, _ in prof if ms >= BIG_LEVEL_MS),
+        "small_levels_ms": small,
+        "small_levels": sum(1 for ms, _ in prof if ms < BIG_LEVEL_MS),
+        "gaps_ms": max(0.0, span_ms - big - small) if prof else None,
+        "kernel_us": [round(ms * 1e3, 1) for ms, _ in prof],
+        "frontier": [fr for _, fr in prof],
+        # visited-set loads and CAS claims of each launch (counting pass): DESIGN.md §3's
+        # attribution of the level times
+        "probes": [int(p) for p, _ in per_launch] if len(per_launch) == len(prof) else None,
+        "cas": [int(c) for _, c in per_launch] if len(per_launch) == len(prof) else None,
+    } if prof else None
+    return roofline, levels
 
 
 if __name__ == "__main__":

@@ -4,6 +4,7 @@
 # (BENCH_ARGS adds bench.py arguments, e.g. BENCH_ARGS="--rm-count 11 --steps 5")
 set -o pipefail
 mkdir -p gpurun_out/sweep
+BENCH_ARGS="--full $BENCH_ARGS"  # the summary below reads the line's `levels`
 for kv in "$@"; do
   name=$(echo "$kv $BENCH_ARGS" | tr ' =/-' '____')
   env $kv timeout -k 10 120 python -u bench.py --steps 20 --warmup 3 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 $BENCH_ARGS > gpurun_out/sweep/$name.json 2> gpurun_out/sweep/$name.err || { echo "fail $kv"; tail -5 gpurun_out/sweep/$name.err; exit 1; }

@@ -7,6 +7,7 @@ TAG=${1:?tag}; REPS=${2:?reps}; shift 2
 K=""
 if [ "$1" = "--parity" ]; then K=$2; shift 2; fi
 [ "$1" = "--" ] && shift
+set -- --full "$@"  # the summaries below read the line's `levels`
 cd "$GRAFT_REPO_ROOT" || exit 1
 export SR_LIB_DIGEST_CHECK=0  # lib_base.so is a build of older sources (see _native.check_digest)
 O=gpurun_out/$TAG

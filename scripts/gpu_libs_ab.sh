@@ -7,6 +7,7 @@ TAG=${1:?tag}; REPS=${2:?reps}; shift 2
 NAMES=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do NAMES+=("$1"); shift; done
 [ "$1" = "--" ] && shift
+set -- --full "$@"  # the summaries below read the line's `levels`
 cd "$GRAFT_REPO_ROOT" || exit 1
 export SR_LIB_DIGEST_CHECK=0  # the variants are builds of other sources (see _native.check_digest)
 O=gpurun_out/$TAG

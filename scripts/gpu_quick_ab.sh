@@ -13,6 +13,7 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_actor.py tests/test_gpu_par
 tail -1 $O/parity.log
 run() {  # label lib -- bench args
     local label=$1 lib=$2; shift 3
+    set -- --full "$@"  # the summary below reads the line's `levels`
     cp "gpurun_ab/lib_$lib.so" "$LIB" || exit 1
     timeout -k 10 200 python -u bench.py --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 "$@" > "$O/$label.json" 2> "$O/$label.err" || { tail -5 "$O/$label.err"; cp gpurun_ab/lib_cur.so "$LIB"; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/$label.json').read().strip().splitlines()[-1]); l=d.get('levels') or {}; print('$label', round(d['ms_per_step'],4), 'small', round(l.get('small_levels_ms',0),4), 'big', round(l.get('big_levels_ms',0),4))"

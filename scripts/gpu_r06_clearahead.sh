@@ -12,7 +12,7 @@ for r in 1 2; do
   for e in "SR_CLEAR_BLOCKS=64" "SR_CLEAR_AHEAD=0" "SR_CLEAR_BLOCKS=16"; do
     for args in "--steps 20" "--rm-count 11 --steps 3 --warmup 1" "--model increment_lock --threads 11 --steps 4 --warmup 1" "--model paxos --clients 3 --steps 20"; do
       tag=$(echo "$args" | tr -d ' -' | cut -c1-20)
-      env $e timeout -k 10 200 python -u bench.py --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 $args \
+      env $e timeout -k 10 200 python -u bench.py --full --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 $args \
           > "$O/${tag}_${e}_r$r.json" 2> "$O/${tag}_${e}_r$r.err" || { tail -5 "$O/${tag}_${e}_r$r.err"; exit 1; }
       python3 -c "import json; d=json.loads(open('$O/${tag}_${e}_r$r.json').read().strip().splitlines()[-1]); l=d.get('levels') or {}; print('$e r$r $args', round(d['ms_per_step'],4), 'span', round(l.get('span_ms',0),4))"
     done

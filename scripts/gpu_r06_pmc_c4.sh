@@ -11,7 +11,7 @@ A="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SAL
 B="TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_ATOMIC_sum GRBM_GUI_ACTIVE"
 for p in A B; do
   timeout -s KILL 240 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d $O/part_$p -o p -- python3 scripts/prof_partitioned.py virtual 8 11 1 > $O/part_$p.log 2>&1 || { echo "part $p failed"; tail -3 $O/part_$p.log; exit 1; }
-  timeout -s KILL 240 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d $O/one_$p -o p -- python3 bench.py --rm-count 11 --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 > $O/one_$p.log 2>&1 || { echo "one $p failed"; tail -3 $O/one_$p.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d $O/one_$p -o p -- python3 bench.py --full --rm-count 11 --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 > $O/one_$p.log 2>&1 || { echo "one $p failed"; tail -3 $O/one_$p.log; exit 1; }
 done
 python3 - $O <<'PY'
 import csv, glob, sys, collections

@@ -13,7 +13,7 @@ for r in 1 2; do
     cp "gpurun_ab/lib_$v.so" "$LIB" || exit 1
     for args in "--rm-count 10 --no-hint-steps 4" "--model increment_lock --threads 11 --no-hint-steps 2"; do
       tag=$(echo "$args" | tr -d ' -' | cut -c1-12)
-      timeout -k 10 200 python -u bench.py --cpu-baseline 0 --config4-steps 0 --steps 1 --warmup 1 $args \
+      timeout -k 10 200 python -u bench.py --full --cpu-baseline 0 --config4-steps 0 --steps 1 --warmup 1 $args \
           > "$O/${v}_${tag}_$r.json" 2> "$O/${v}_${tag}_$r.err" || { tail -5 "$O/${v}_${tag}_$r.err"; cp gpurun_ab/lib_new.so "$LIB"; exit 1; }
       python3 -c "import json; d=json.loads(open('$O/${v}_${tag}_$r.json').read().strip().splitlines()[-1]); n=d['no_hint']; print('$v r$r $args', 'no_hint', round(n['ms_per_step'],3))"
     done

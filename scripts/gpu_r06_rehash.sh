@@ -12,7 +12,7 @@ for r in 1; do
   for e in 1 0; do
     for args in "--rm-count 9 --no-hint-steps 10" "--rm-count 10 --no-hint-steps 3" "--model increment_lock --threads 11 --no-hint-steps 2"; do
       tag=$(echo "$args" | tr -d ' -' | cut -c1-24)
-      SR_REHASH_RANGES=$e timeout -k 10 200 python -u bench.py --cpu-baseline 0 --config4-steps 0 --steps 2 --warmup 1 $args \
+      SR_REHASH_RANGES=$e timeout -k 10 200 python -u bench.py --full --cpu-baseline 0 --config4-steps 0 --steps 2 --warmup 1 $args \
           > "$O/${tag}_e${e}_r$r.json" 2> "$O/${tag}_e${e}_r$r.err" || { tail -5 "$O/${tag}_e${e}_r$r.err"; exit 1; }
       python3 -c "import json; d=json.loads(open('$O/${tag}_e${e}_r$r.json').read().strip().splitlines()[-1]); n=d['no_hint']; print('ranges=$e r$r $args', 'hinted', round(d['ms_per_step'],3), 'no_hint', round(n['ms_per_step'],3), round(n['vs_value'],3))"
     done

@@ -18,7 +18,7 @@ REQ="TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_ATOMIC_sum"
 timeout -k 10 120 rocprofv3 --pmc $REQ --kernel-trace --output-format csv -d $O/ceiling -o c -- ./scripts/microbench_random > $O/ceiling.log 2>&1 || { echo "ceiling pass failed"; tail -5 $O/ceiling.log; exit 1; }
 run() {  # label, bench args
     local tag=$1; shift
-    local B="bench.py --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 $*"
+    local B="bench.py --full --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 $*"
     timeout -k 10 180 rocprofv3 --pmc $REQ --kernel-trace --output-format csv -d $O/$tag/req -o r -- python3 $B > $O/$tag.req.log 2>&1 || { echo "$tag req pass failed"; tail -5 $O/$tag.req.log; return 1; }
     timeout -k 10 180 rocprofv3 --pmc TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d $O/$tag/rd -o r -- python3 $B > $O/$tag.rd.log 2>&1 || { echo "$tag rd pass failed"; return 1; }
     timeout -k 10 180 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/$tag/wr -o r -- python3 $B > $O/$tag.wr.log 2>&1 || { echo "$tag wr pass failed"; return 1; }

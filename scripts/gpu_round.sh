@@ -16,7 +16,7 @@ mkdir -p "$O"
 want() { [ "$WHAT" = all ] || [ "$WHAT" = "$1" ]; }
 b() {
     local name=$1; shift
-    timeout -k 10 300 python -u bench.py "$@" > "$O/$name.json" 2> "$O/$name.err" || { echo "bench $name failed"; tail -20 "$O/$name.err"; return 1; }
+    timeout -k 10 300 python -u bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err" || { echo "bench $name failed"; tail -20 "$O/$name.err"; return 1; }
     tail -1 "$O/$name.json"
 }
 
@@ -36,9 +36,9 @@ if want bench; then
 fi
 if want prof; then
     export TMPDIR=/tmp
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o bench -- python3 bench.py --steps 5 --warmup 2 --cpu-baseline 0 --config4-steps 0 > "$O/prof.log" 2>&1 || { echo "rocprof failed"; tail -20 "$O/prof.log"; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o bench -- python3 bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --config4-steps 0 > "$O/prof.log" 2>&1 || { echo "rocprof failed"; tail -20 "$O/prof.log"; exit 1; }
     tail -1 "$O/prof.log"
-    bash scripts/ktrace.sh "$TAG/kt_2pc" --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 || exit 1
+    bash scripts/ktrace.sh "$TAG/kt_2pc" --full --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 || exit 1
     python3 scripts/ktrace_levels.py "$O/kt_2pc/trace_kernel_trace.csv"
 fi
 if want pmc; then

@@ -10,7 +10,7 @@ mkdir -p $O
 want() { [ "$WHAT" = all ] || [ "$WHAT" = "$1" ]; }
 b() {
     local name=$1; shift
-    timeout -k 10 300 python -u bench.py "$@" > "$O/$name.json" 2> "$O/$name.err" || { echo "bench $name failed"; tail -20 "$O/$name.err"; return 1; }
+    timeout -k 10 300 python -u bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err" || { echo "bench $name failed"; tail -20 "$O/$name.err"; return 1; }
     python3 -c "import json,sys; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); l=d.get('levels') or {}; print('$name', round(d['ms_per_step'],4), 'ms', 'big', round(l.get('big_levels_ms') or 0,4), 'small', round(l.get('small_levels_ms') or 0,4), 'gaps', round(l.get('gaps_ms') or 0,4))"
 }
 if want tests; then

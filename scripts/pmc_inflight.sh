@@ -14,7 +14,7 @@ B="TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum GRBM_GUI_ACTIVE"
 C="TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_STALL_INFLIGHT_MAX_sum TCP_UTCL1_STALL_MULTI_MISS_sum GRBM_GUI_ACTIVE"
 for n in 9 11; do
   for p in A B C; do
-    timeout -s KILL 180 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d $O/n${n}_$p -o p -- python3 bench.py \
+    timeout -s KILL 180 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d $O/n${n}_$p -o p -- python3 bench.py --full \
         --rm-count $n --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 > $O/n${n}_$p.log 2>&1 \
         || { echo "n$n pass $p failed"; tail -3 $O/n${n}_$p.log; exit 1; }
   done

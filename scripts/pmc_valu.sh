@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out/pmc_valu
 mkdir -p $O
 for n in 9 11; do
-  timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM --kernel-trace --output-format csv -d $O/n$n -o p -- python3 bench.py --rm-count $n --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 > $O/n$n.log 2>&1 || { echo "n$n failed"; tail -3 $O/n$n.log; exit 1; }
+  timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM --kernel-trace --output-format csv -d $O/n$n -o p -- python3 bench.py --full --rm-count $n --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 > $O/n$n.log 2>&1 || { echo "n$n failed"; tail -3 $O/n$n.log; exit 1; }
 done
 python3 - $O <<'PY'
 import csv, glob, sys, collections

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 C=${1:-3}; LPC=${2:-29}; SPC=${3:-2420477}
 O=gpurun_out/pmc_valu_paxos_c$C
 mkdir -p $O
-timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM --kernel-trace --output-format csv -d $O/p3 -o p -- python3 bench.py --model paxos --clients $C --steps 3 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 > $O/p3.log 2>&1 || { echo "pmc failed"; tail -3 $O/p3.log; exit 1; }
+timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM --kernel-trace --output-format csv -d $O/p3 -o p -- python3 bench.py --full --model paxos --clients $C --steps 3 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 > $O/p3.log 2>&1 || { echo "pmc failed"; tail -3 $O/p3.log; exit 1; }
 python3 - $O $C $LPC $SPC <<'PY'
 import csv, glob, sys, collections
 sys.path.insert(0, 'scripts')

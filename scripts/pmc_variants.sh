@@ -17,7 +17,7 @@ B="TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_ATOMIC_su
 for i in "${!ENVS[@]}"; do
   for p in A B; do
     env ${ENVS[$i]} timeout -s KILL 120 rocprofv3 --pmc ${!p} --kernel-trace --output-format csv -d "$O/v${i}_$p" -o p -- \
-        python3 bench.py --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 "$@" > "$O/v${i}_$p.log" 2>&1 \
+        python3 bench.py --full --steps 1 --warmup 1 --cpu-baseline 0 --config4-steps 0 --no-hint-steps 0 "$@" > "$O/v${i}_$p.log" 2>&1 \
         || { echo "variant $i pass $p failed"; tail -3 "$O/v${i}_$p.log"; exit 1; }
   done
 done

@@ -33,6 +33,15 @@ def test_world_size_must_match_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 4" in (r.stderr + r.stdout)
 
 
+def test_full_and_dump_outputs_options(tmp_path):
+    # both options parse; a dry run stops before any measurement, so nothing is written
+    r = run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path / "out"),
+             "--dry-run"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["dry_run"] is True
+    assert not (tmp_path / "out").exists()
+
+
 def test_single_gpu_dry_run():
     r = run(["--dry-run"])
     assert r.returncode == 0

@@ -130,7 +130,7 @@ def test_bench_two_ranks_rehearsal():
     # transport: one JSON line from rank 0, the partitioned check on the direct exchange.
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--comm", "shm", "--steps", "2",
-                        "--warmup", "1", "--config4-steps", "0"], capture_output=True, text=True, timeout=300, cwd=root)
+                        "--warmup", "1", "--full", "--config4-steps", "0"], capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
