@@ -34,7 +34,9 @@
  * Errors: the reference panics (zero fingerprint src/lib.rs:310, path nondeterminism
  * src/checker/path.rs:35-79, worker panics src/checker/bfs.rs:302). Here every call returns a
  * status (SR_OK or a negative SR_ERR_*) and sr_last_error() describes the last failure on the
- * calling thread.
+ * calling thread. A check whose model reaches a state that its encoding cannot hold (the device's
+ * ERR_MODEL bit: an actor network past its slots) ends with SR_ERR_UNSUPPORTED, "<model>: a state
+ * exceeded its encoding (network slots)", without a capacity restart; its counts are not results.
  *
  * Threading: spawn returns immediately; the level loop runs on a host driver thread bound to one
  * HIP device. Counters are readable while it runs (like the reference's atomics).
@@ -61,7 +63,10 @@ enum sr_model_id {
     SR_MODEL_PINGPONG = 9,        /* (max_nat<=14, lossy, duplicating, maintains_history)
                                      src/actor/actor_test_util.rs:4-96                     */
     SR_MODEL_ACTOR_FIXTURE = 10,  /* (kind: 0 undeliverable envelope, 1 timer) src/actor/model.rs:697-733 */
-    SR_MODEL_ABD = 11,            /* (client_count<=3, server_count<=3) examples/linearizable-register.rs */
+    SR_MODEL_ABD = 11,            /* (client_count<=6, server_count<=4; <=8 actors) examples/linearizable-register.rs.
+                                     The network of (C, S) holds at most B = C * max(1, 3d + S - 1, 4d)
+                                     envelopes, d = S - majority: 8 slots when C, S <= 3 and B <= 8, else
+                                     16 (B <= 16), else 32 (states then describe 32 envelopes) */
     SR_MODEL_SINGLE_COPY = 12     /* (client_count<=6, server_count; <=8 actors) examples/single-copy-register.rs */
 };
 

@@ -28,6 +28,10 @@
  *                                             (2pc reports all of them: 37% of successors)
  *             SR_HD canonical(s, out)         a canonical representative under the model's symmetry
  *                                             (the opt-in symmetry_canonical reduction)
+ *             SR_HD bool faulted(s)           s lost information when it was built (a state its
+ *                                             encoding cannot hold): the check ends with
+ *                                             SR_ERR_UNSUPPORTED; model_name() (host) names the
+ *                                             model in that error
  *
  * Equal states must have equal words (the words ARE the state), and slots are enumerated in the
  * reference's `actions()` order, so FIFO runs reproduce the reference's visit order and paths.

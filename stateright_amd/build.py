@@ -15,10 +15,10 @@ ROOT = os.path.dirname(HERE)
 CDIR = os.path.join(HERE, "csrc")
 SRC = os.path.join(CDIR, "engine.hip")
 UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip", "reg_increment_lock.hip",
-         "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip"]
+         "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
                                                 "dist.hpp", "dist_host.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
-                                                "actor.hpp"]]
+                                                "actor.hpp", "abd_wide.hpp"]]
 HEADERS = [os.path.join(ROOT, "include", f) for f in ("stateright_gpu.h", "stateright_gpu_model.hpp")]
 OUT = os.path.join(HERE, "libstateright_gpu.so")
 OBJDIR = os.path.join(HERE, "build")
@@ -103,7 +103,7 @@ def _library(force, verbose, pool):
         return OUT
 
     # the largest units first, so the slowest compiles start first
-    order = sorted(UNITS, key=lambda u: 0 if u.startswith("reg_paxos") or u == "reg_registers.hip" else 1)
+    order = sorted(UNITS, key=lambda u: 0 if u.startswith("reg_paxos") or u.startswith("reg_registers") else 1)
     return [pool.submit(link, [pool.submit(compile_unit, u) for u in order])]
 
 

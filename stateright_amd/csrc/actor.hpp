@@ -4,7 +4,8 @@
 // the boundary and the properties), with the reference's actor fixtures on top:
 //   PingPongSysT  ping-pong (src/actor/actor_test_util.rs:4-96), lossy / duplicating options
 //   FixtureSys    the undeliverable-message and timer fixtures (src/actor/model.rs:697-733)
-//   AbdSys        the ABD linearizable register (examples/linearizable-register.rs)
+//   AbdSys        the ABD linearizable register (examples/linearizable-register.rs), 8 network
+//                 slots; abd_wide.hpp has the 16- and 32-slot encodings of the larger systems
 //   SingleCopySys the single-copy register (examples/single-copy-register.rs)
 // The CPU restatement the encodings are tested against is oracle/actor.hpp.
 //
@@ -50,7 +51,10 @@ struct Out {
     SR_HD void cancel_timer() { kind[n] = CANCEL_TIMER, dst[n] = 0, msg[n] = 0, ++n; }
 };
 
-constexpr u64 OVERFLOW_BIT = 1ull << 51;  // a network past its K slots (refused at make(); never set)
+// A network past its K slots (its largest envelope is dropped), or a cancelled timer that was never
+// set (the reference panics). The state is no state of the reference's: `faulted` reports it, and the
+// engines end the check with SR_ERR_UNSUPPORTED (kernels.hpp ERR_MODEL).
+constexpr u64 OVERFLOW_BIT = 1ull << 51;
 
 template <class Sys>
 struct ActorGpu : Sys {
@@ -61,6 +65,9 @@ struct ActorGpu : Sys {
     SR_HD static u32 slot(const u64* s, int k) { return (u32)(s[AW + k / 2] >> (32 * (k & 1))); }
     SR_HD static u32 tlen(const u64* s) { return (u32)(s[0] >> 52 & 15); }
     SR_HD static u32 tmask(const u64* s) { return (u32)(s[0] >> 56 & 255); }
+
+    SR_HD bool faulted(const u64* s) const { return (s[0] & OVERFLOW_BIT) != 0; }
+    const char* model_name() const { return Sys::NAME; }
 
     int max_actions() const { return 2 * K + 8; }
     int max_out_degree() const { return 2 * K + (int)this->nact(); }
@@ -254,6 +261,7 @@ struct ActorGpu : Sys {
 template <int KK>
 struct PingPongSysT {
     static constexpr int K = KK, AW = 1, NACT = 2, NPROPS = 6, NET = KK;
+    static constexpr const char* NAME = "ping-pong";
     static constexpr u32 MAX_NAT = KK / 2 - 1 < 14 ? KK / 2 - 1 : 14;
     u32 max_nat = 1;
     bool lossy = false, duplicating = true, maintains_history = false;
@@ -322,6 +330,7 @@ struct PingPongSysT {
 // ---------------------------------------------------------------------------------------------
 struct FixtureSys {
     static constexpr int K = 4, AW = 1, NACT = 1, NPROPS = 1, NET = 4;
+    static constexpr const char* NAME = "actor fixture";
     int kind = 0;
     bool lossy = false, duplicating = true;
     SR_HD u32 nact() const { return 1; }
@@ -368,6 +377,7 @@ struct FixtureSys {
 // ---------------------------------------------------------------------------------------------
 struct AbdSys {
     static constexpr int K = 8, AW = 4, NACT = 6, NPROPS = 2, NET = 16;
+    static constexpr const char* NAME = "abd";
     enum Kind : u32 { PUT, GET, PUTOK, GETOK, QUERY, ACKQUERY, RECORD, ACKRECORD };
     u32 S = 2, C = 2;
     bool lossy = false, duplicating = false;
@@ -625,6 +635,7 @@ struct AbdSys {
     int undescribe_fields(const i64* d, u64* s) const {
         int k = 0;
         const int width = 8 + (int)S;
+        u32 completed[px::MAX_CLIENTS] = {};
         for (u32 id = 0; id < S + C; ++id) {
             const int base = k;
             if (id < S) {
@@ -648,11 +659,12 @@ struct AbdSys {
             } else {
                 const i64 aw = d[k], ops = d[k + 1];
                 s[0] = setf(s[0], 16 + 7 * (int)(id - S), 7, (aw >= 0 ? 1u | (u32)aw << 1 : 0u) | (u32)ops << 5);
+                completed[id - S] = ops > 0 ? (u32)ops - 1 : 0u;  // op_count counts the op in flight too
             }
             k = base + width;
         }
         px::Tables& t = px::tables((int)C, -1);
-        s[0] |= t.hist_index(d + k);
+        s[0] |= t.hist_index(d + k, completed);
         return k + history_width();
     }
 };
@@ -671,6 +683,7 @@ struct AbdSys {
 // ---------------------------------------------------------------------------------------------
 struct SingleCopySys {
     static constexpr int K = 6, AW = 3, NACT = 8, NPROPS = 2, NET = 8;
+    static constexpr const char* NAME = "single-copy register";
     enum Kind : u32 { PUT, GET, PUTOK, GETOK };
     u32 S = 1, C = 2;
     bool lossy = false, duplicating = false;

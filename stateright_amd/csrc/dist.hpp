@@ -101,10 +101,14 @@ inline size_t row_words(u32 T, u32 nprops) { return (size_t)T + ROW_DISC + nprop
 // A level's error bits (OR over every row), acted on by every rank at the same level and in this
 // order: an exchange error wins over the capacity errors (a corrupt record can overflow a bucket,
 // and a capacity restart would keep the direct exchange).
-inline void throw_row_errors(u64 glob_err, u32 level) {
+// A state past its model's encoding (ERR_MODEL, `fault`: model_fault_text) is no capacity error: it
+// fails the check on every rank (OUT_ERROR in the vote).
+inline void throw_row_errors(u64 glob_err, u32 level,
+                             const std::string& fault = "model: a state exceeded its encoding (network slots)") {
     if (glob_err & ERR_EXCHANGE)
         throw Error(ERR_CODE_EXCHANGE, "direct exchange: a receive slot failed its sequence tag or checksum (level " +
                                            std::to_string(level) + ")");
+    if (glob_err & ERR_MODEL) throw Error(SR_ERR_UNSUPPORTED, fault);
     if (glob_err & ERR_TABLE_FULL) throw Error(SR_ERR_CAPACITY, "visited set probe limit exceeded");
     if (glob_err & ERR_FRONTIER_OVERFLOW) throw Error(SR_ERR_CAPACITY, "frontier or send bucket overflow");
 }
@@ -1716,7 +1720,7 @@ class DistEngine final : public EngineBase {
                 gl_lstart_[q].push_back(gl_off_[q]);  // arena offset of this level in partition q
                 gl_off_[q] += all[q * RW + T_ + ROW_N];
             }
-            throw_row_errors(sm.err, level);
+            throw_row_errors(sm.err, level, model_fault_text(m_));
             for (auto& p : parts_) {
                 const u64* row = &all[p.id * RW];
                 if (level > lvl0_) {
@@ -1915,6 +1919,7 @@ class DistEngine final : public EngineBase {
                 1u, ppw_log2, filt_log2_, SlotWork{});
             SR_HIP(hipGetLastError());
             wait(p0);
+            if (p0.last.err & ERR_MODEL) throw Error(SR_ERR_UNSUPPORTED, model_fault_text(m_));
             if (p0.last.err) {
                 head_failed_ = true;
                 throw Error(SR_ERR_CAPACITY, "replicated head: scratch buffers too small");
@@ -2278,7 +2283,7 @@ class DistEngine final : public EngineBase {
             // stall the vote until SR_PEER_TIMEOUT_MS. An exchange error wins over a
             // capacity error (a corrupt record can overflow a bucket; a capacity restart would keep
             // the direct exchange).
-            throw_row_errors(glob_err, level);
+            throw_row_errors(glob_err, level, model_fault_text(m_));
             // The last level's insert has no later rows: its own check is read where the search
             // ends (the vote then makes every rank redo the check).
             auto own_exchange_check = [&] {

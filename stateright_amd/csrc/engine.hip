@@ -4,7 +4,7 @@
 #include "registry.hpp"
 #include "dgraph.hpp"
 #include "paxos.hpp"
-#include "actor.hpp"
+#include "abd_wide.hpp"
 #include "dist_host.hpp"
 
 namespace sr {
@@ -335,9 +335,7 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
         }
         case SR_MODEL_ABD: {
             need(1);
-            AbdRegister m;
-            static_cast<act::AbdSys&>(m) = act::AbdSys::make((int)p[0], np > 1 ? (int)p[1] : 2, -1);
-            return f(m);
+            return with_abd_model((int)p[0], np > 1 ? (int)p[1] : 2, -1, [&](const auto& m) -> i64 { return f(m); });
         }
         case SR_MODEL_SINGLE_COPY: {
             need(1);
@@ -988,4 +986,5 @@ extern "C" int64_t sr_timeline_fetch(int32_t device, uint64_t* out, int64_t cap)
 #include "reg_paxos_wide.hip"
 #include "reg_ping_pong.hip"
 #include "reg_registers.hip"
+#include "reg_registers_wide.hip"
 #endif

@@ -796,6 +796,7 @@ class Engine final : public EngineBase {
         }
         std::atomic_thread_fence(std::memory_order_acquire);
         std::memcpy(&lc_, (const void*)&ctx_->hc[seq & 1], sizeof(lc_));
+        if (lc_.err & ERR_MODEL) throw Error(SR_ERR_UNSUPPORTED, model_fault_text(m_));  // (no restart helps)
         if (recoverable && (lc_.err == ERR_TABLE_FULL || lc_.err == ERR_DEFERRED)) return false;
         if (lc_.err & ERR_TABLE_FULL) throw Error(SR_ERR_CAPACITY, "visited set probe limit exceeded");
         if (lc_.err & ERR_DEFERRED) throw Error(SR_ERR_CAPACITY, "deferred level");

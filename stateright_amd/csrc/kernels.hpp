@@ -71,7 +71,10 @@ constexpr int expand_wpb() { return M::W >= 4 ? 4 : SR_NARROW_WPB; }
 // not match what its source stored (kernels_dist.hpp): the check is redone on the collective exchange.
 // ERR_DEFERRED: a speculative launch found its frontier too large for the room the host left in the
 // visited set or the arena and expanded nothing (the host grows them and launches the level again).
-enum ErrBits { ERR_TABLE_FULL = 1, ERR_FRONTIER_OVERFLOW = 2, ERR_PEER_TIMEOUT = 4, ERR_EXCHANGE = 8, ERR_DEFERRED = 16 };
+// ERR_MODEL: a new state exceeded its model's encoding (the model's optional `faulted` hook,
+// models.hpp): the check ends with SR_ERR_UNSUPPORTED, and no restart with larger buffers helps.
+enum ErrBits { ERR_TABLE_FULL = 1, ERR_FRONTIER_OVERFLOW = 2, ERR_PEER_TIMEOUT = 4, ERR_EXCHANGE = 8, ERR_DEFERRED = 16,
+               ERR_MODEL = 32 };
 
 // Two slot encodings ("Visited set"):
 //  * fingerprint mode (qbits == 0): a slot holds the 64-bit fingerprint. Exact for one-word states
@@ -722,6 +725,11 @@ __device__ __forceinline__ void eval_props(const M& m, const u64* s, u32 rank, u
         int p = __builtin_ctz(und);
         und &= und - 1;
         if (m.discovers(p, s)) atomicMin(&lc->disc[p], rank);
+    }
+    // every kernel that appends a new state evaluates its properties here, so this is where a
+    // state past its model's encoding is reported (models without the hook: the same code as before)
+    if constexpr (has_faulted<M>::value) {
+        if (m.faulted(s)) atomicOr(&lc->err, (u32)ERR_MODEL);
     }
 }
 

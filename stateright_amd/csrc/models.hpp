@@ -96,6 +96,26 @@ template <class M>
 struct has_owner_key<M, std::void_t<decltype(std::declval<const M&>().owner_key((const u64*)nullptr, (u64*)nullptr))>>
     : std::true_type {};
 
+// Models whose encoding can be exceeded by a reachable state (`faulted(s)`: the state s lost
+// information when it was built, e.g. an actor network past its slots). Every kernel that evaluates
+// a new state's properties asks the hook and ORs ERR_MODEL into the level's err word (kernels.hpp
+// eval_props); the engines end the check with SR_ERR_UNSUPPORTED (`model_fault`), with no capacity
+// restart. `model_name()` (optional, host) names the model in that error.
+template <class M, class = void>
+struct has_faulted : std::false_type {};
+template <class M>
+struct has_faulted<M, std::void_t<decltype(std::declval<const M&>().faulted((const u64*)nullptr))>> : std::true_type {};
+template <class M, class = void>
+struct has_model_name : std::false_type {};
+template <class M>
+struct has_model_name<M, std::void_t<decltype(std::declval<const M&>().model_name())>> : std::true_type {};
+template <class M>
+inline std::string model_fault_text(const M& m) {
+    std::string name = "model";
+    if constexpr (has_model_name<M>::value) name = m.model_name();
+    return name + ": a state exceeded its encoding (network slots)";
+}
+
 // Init states (`Model::init_states`, src/lib.rs:163). A model writes its init states into a host
 // buffer of W words each; the engine sizes that buffer from the model's optional `init_count()`,
 // or for MAX_INIT_STATES states when the model has none (the documented bound of the GpuModel

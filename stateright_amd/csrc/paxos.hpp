@@ -320,18 +320,25 @@ struct Tables {
     std::vector<u8> h_lin;    // linearizable per history
     std::vector<Hist> hists;  // the interned histories (describe)
     std::map<int, std::pair<u16*, u8*>> dev;  // device copies (process lifetime)
-    // The index of a described history (undescribe); throws if no reachable history has it.
-    u32 hist_index(const i64* d) {
+    // The index of a described history (undescribe), given every client's completed ops (its
+    // op_count - 1, described with the actors); throws if no reachable history has it. The
+    // description alone does not tell a lone client's histories apart: with C = 1 it is the Get's
+    // returned value only, -1 both while the Put is in flight and while the Get is (with more
+    // clients the Get's `last` entries tell), so the completed ops are part of the key.
+    u32 hist_index(const i64* d, const u32* completed) {
         static std::mutex mu;
         std::lock_guard<std::mutex> g(mu);
         if (by_desc_.empty()) {
-            std::vector<i64> k((size_t)(C * C));
+            std::vector<i64> k((size_t)(C * C + C));
             for (size_t h = 0; h < hists.size(); ++h) {
                 describe_hist(hists[h], C, k.data());
+                for (int c = 0; c < C; ++c) k[(size_t)(C * C + c)] = (i64)hists[h].done[c].size();
                 by_desc_.emplace(k, (u32)h);
             }
         }
-        auto it = by_desc_.find(std::vector<i64>(d, d + C * C));
+        std::vector<i64> key(d, d + C * C);
+        for (int c = 0; c < C; ++c) key.push_back((i64)completed[c]);
+        auto it = by_desc_.find(key);
         if (it == by_desc_.end()) throw Error(SR_ERR_ARG, "register history: no reachable history has this description");
         return it->second;
     }

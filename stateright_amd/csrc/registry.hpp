@@ -44,6 +44,7 @@ std::unique_ptr<EngineBase> reg_increment_lock(const EngineArgs& a);  // increme
 std::unique_ptr<EngineBase> reg_paxos(const EngineArgs& a);           // paxos, 1-4 clients (W = 11)
 std::unique_ptr<EngineBase> reg_paxos_wide(const EngineArgs& a);      // paxos, 5-6 clients (W = 12)
 std::unique_ptr<EngineBase> reg_ping_pong(const EngineArgs& a);       // ping-pong
-std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD and the single-copy register
+std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 slots) and the single-copy register
+std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
 
 }  // namespace sr

@@ -197,7 +197,15 @@ class SingleCopyRegister(_Model):
 class AbdRegister(_Model):
     """The ABD linearizable register `AbdModelCfg { client_count, server_count }.into_model()`
     (examples/linearizable-register.rs:192-229): AbdActor servers, RegisterActor clients, a
-    non-duplicating network and a linearizability history."""
+    non-duplicating network and a linearizability history.
+
+    Limits: `client_count` in 1..=6, `server_count` in 1..=4, at most 8 actors. The network of
+    (C, S) holds at most B = C * max(1, 3d + S - 1, 4d) envelopes (d = S - majority: late replies
+    are never removed), and the encoding follows from B: 8 network slots for C, S <= 3 with B <= 8
+    (the states and fingerprints of those systems are what they always were), 16 slots for B <= 16
+    (e.g. (4..6, 2), (2, 3), (3, 3), (1, 4), (2, 4)), and 32 slots for (4, 3), (5, 3), (3, 4) and
+    (4, 4). Only the 32-slot encoding describes 32 envelopes per state; the others describe 16, as
+    the CPU oracle does. A state past its slots fails `join()` with SR_ERR_UNSUPPORTED."""
     MODEL_ID = N.SR_MODEL_ABD
 
     def __init__(self, client_count=2, server_count=2):
