@@ -147,6 +147,9 @@ typedef struct sr_stats {
                                     or a peer's flag timed out (the result is then still exact)    */
     uint32_t owner_key;          /* partitioned search: 1 = states are owned by the model's owner key
                                     (a projection most actions keep), 0 = by fingerprint          */
+    uint32_t balanced_levels;    /* FAST order: expand launches that cut their level into equal
+                                    workgroup shares from the real frontier size (SR_BALANCE=0: 0) */
+    uint32_t reserved0;          /* (keeps the size a multiple of 8) */
 } sr_stats;
 
 typedef struct sr_bfs sr_bfs;
@@ -317,6 +320,11 @@ const char* sr_build_digest(void);
 /* Host-only self-test of the visited set's quotient encoding (kernels.hpp): the key permutation is
  * a bijection and slot values decode to their keys. SR_OK or SR_ERR_ARG (sr_last_error). */
 int32_t sr_selftest_tables(void);
+/* Host-only self-test of the FAST expansion's level geometry (kernels.hpp level_geometry): the
+ * workgroup / chunk / wave / lane shares of a level, fixed and balanced, take every parent of the
+ * frontier exactly once over a range of frontier sizes, grids, parents-per-wave caps and waves per
+ * workgroup; balanced shares are equal to within one chunk. SR_OK or SR_ERR_ARG (sr_last_error). */
+int32_t sr_selftest_level_geometry(void);
 /* Host-only self-check of the compiled-in model encodings: every slot a model's optional
  * `self_loops` reports (counted by the FAST expansion without being generated) is enabled and
  * returns the state itself, over every reachable state of 2pc N=1..7 (and its canonical form);

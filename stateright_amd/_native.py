@@ -66,6 +66,8 @@ class sr_stats(ctypes.Structure):
         ("table_doublings", ctypes.c_uint32),
         ("exchange_fallbacks", ctypes.c_uint32),
         ("owner_key", ctypes.c_uint32),
+        ("balanced_levels", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
     ]
 
     def as_dict(self):
@@ -163,6 +165,7 @@ SIGNATURES = [
     ("sr_device_synchronize", ctypes.c_int32, [ctypes.c_int32]),
     ("sr_build_digest", ctypes.c_char_p, []),
     ("sr_selftest_tables", ctypes.c_int32, []),
+    ("sr_selftest_level_geometry", ctypes.c_int32, []),
     ("sr_selftest_models", ctypes.c_int32, []),
     ("sr_gpu_bfs_spawn_plugin", _P, [_P, _I64P, ctypes.c_int32, ctypes.POINTER(sr_opts)]),
     ("sr_gpu_bfs_spawn_plugin_partitioned", _P, [_P, _P, ctypes.c_int32, _I64P, ctypes.c_int32,

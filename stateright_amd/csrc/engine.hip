@@ -862,6 +862,96 @@ int32_t sr_selftest_tables(void) {
     return SR_OK;
 }
 
+// expand_fast's level geometry (kernels.hpp LevelGeom / level_geometry) walked on the host the way
+// the kernel walks it: workgroup b from first_chunk in steps of stride while the chunk starts below
+// hi, wave wid's lanes l < pw at wave_first + l below chunk_end. A wave's ranks are an interval, so
+// the walk records intervals: they must tile [lo, hi) (every parent exactly once, none outside).
+// Also pw <= cap, cw <= wpb cap, workgroup shares within one chunk width of each other, and with
+// the switch off the waves of the shift formula the kernel used before.
+static bool check_level_geometry(u32 nblk, std::vector<u32>& stamp, std::vector<u32>& end, u32& gen,
+                                 const std::vector<u32>& ns, std::string& why) {
+    for (u32 wpb : {4u, 8u})
+        for (u32 cap_log2 = 2; cap_log2 <= 6; ++cap_log2)
+            for (int balanced = 0; balanced < 2; ++balanced)
+                for (u32 n : ns) {
+                    const u32 cap = 1u << cap_log2, lo = n & 1 ? 77u : 0u, hi = lo + n;
+                    const LevelGeom g = level_geometry(n, nblk, wpb, cap, balanced != 0);
+                    auto fail = [&](const char* what) {
+                        why = std::string("level geometry: ") + what + " at n=" + std::to_string(n) + " nblk=" +
+                              std::to_string(nblk) + " cap=" + std::to_string(cap) + " wpb=" + std::to_string(wpb) +
+                              (balanced ? " balanced" : " fixed");
+                        return false;
+                    };
+                    if (g.pw == 0 || g.pw > cap || g.cw == 0 || g.cw > wpb * cap) return fail("pw or cw out of range");
+                    if (!balanced && (g.pw != cap || g.cw != wpb * cap)) return fail("fixed geometry changed");
+                    ++gen;
+                    u64 intervals = 0, share_min = ~0ull, share_max = 0;
+                    for (u32 b = 0; b < nblk; ++b) {
+                        u64 share = 0;
+                        u64 j = 0;  // the workgroup's j-th chunk
+                        for (u64 c0 = g.first_chunk(lo, b); c0 < hi; c0 += g.stride(nblk), ++j) {
+                            const u32 lim = g.chunk_end(c0, hi);
+                            for (u32 wid = 0; wid < wpb; ++wid) {
+                                const u64 w0 = g.wave_first(c0, wid);
+                                const u64 w1 = std::min<u64>(w0 + g.pw, lim);  // lanes l < pw with w0 + l < lim
+                                if (!balanced) {  // the shift formula: lanes l < 2^cap_log2 with rank < hi
+                                    const u64 o0 = lo + (((u64)b + j * nblk) * wpb << cap_log2) + ((u64)wid << cap_log2);
+                                    const u64 o1 = std::min<u64>(o0 + cap, hi);
+                                    if (o0 < o1 ? o0 != w0 || o1 != w1 : w0 < w1) return fail("differs from the shift formula");
+                                }
+                                if (w1 <= w0) continue;
+                                if (w0 < lo || w1 > hi) return fail("a parent outside the frontier");
+                                if (stamp[w0 - lo] == gen) return fail("a parent taken twice");
+                                stamp[w0 - lo] = gen;
+                                end[w0 - lo] = (u32)(w1 - lo);
+                                share += w1 - w0;
+                                ++intervals;
+                            }
+                        }
+                        share_min = std::min(share_min, share);
+                        share_max = std::max(share_max, share);
+                    }
+                    u64 followed = 0;
+                    u32 pos = 0;
+                    while (pos < n) {
+                        if (stamp[pos] != gen) return fail("a parent not taken");
+                        pos = end[pos];
+                        ++followed;
+                    }
+                    if (pos != n || followed != intervals) return fail("waves overlap");
+                    if (share_max - share_min > g.cw) return fail("workgroup shares differ by more than one chunk");
+                }
+    return true;
+}
+
+int32_t sr_selftest_level_geometry(void) {
+    std::vector<u32> ns;
+    for (u32 n = 0; n <= 2048; ++n) ns.push_back(n);
+    for (u32 k = 12; k <= 21; ++k)
+        for (u32 n : {(1u << k) - 1, 1u << k, (1u << k) + 1}) ns.push_back(n);
+    std::vector<u32> nblks;
+    for (u32 b = 1; b <= 48; ++b) nblks.push_back(b);
+    for (u32 b : {1535u, 1536u, 1537u}) nblks.push_back(b);
+    // (one worker per slice of the workgroup counts: ~10^9 wave intervals in all)
+    const u32 workers = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    std::vector<std::string> why(workers);
+    std::vector<std::thread> pool;
+    for (u32 w = 0; w < workers; ++w)
+        pool.emplace_back([&, w] {
+            std::vector<u32> stamp((1u << 21) + 2, 0), end((1u << 21) + 2, 0);
+            u32 gen = 0;
+            for (size_t i = w; i < nblks.size() && why[w].empty(); i += workers)
+                check_level_geometry(nblks[i], stamp, end, gen, ns, why[w]);
+        });
+    for (auto& t : pool) t.join();
+    for (auto& s : why)
+        if (!s.empty()) {
+            set_error(s);
+            return SR_ERR_ARG;
+        }
+    return SR_OK;
+}
+
 // PaxosHist::linearizable (the cluster-graph test) against PaxosHist::linearizable_search (the
 // tester's serialization search) on random histories of the register clients' protocol (every
 // client: Write invoked at init; on its completion the Read is invoked, recording how many ops every

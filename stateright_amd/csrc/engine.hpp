@@ -331,6 +331,8 @@ class Engine final : public EngineBase {
         if (const char* e = std::getenv("SR_CHAIN_MAX")) chain_max_ = (u64)std::max(0ll, std::atoll(e));
         if (const char* e = std::getenv("SR_TABLE_KIND")) table_kind_ = std::atoi(e);
         if (const char* e = std::getenv("SR_TABLE_RECYCLE")) table_recycle_ = std::atoi(e) != 0;
+        if (const char* e = std::getenv("SR_BALANCE")) balance_ = std::atoi(e) != 0;
+        if (const char* e = std::getenv("SR_BALANCE_MIN")) balance_min_ = (u64)std::max(0ll, std::atoll(e));
     }
     ~Engine() override = default;
 
@@ -1319,22 +1321,57 @@ class Engine final : public EngineBase {
     // printed with verbose=1. SR_GRID_MAX > 0 overrides it (<= 0 or unparsable: the default).
     // The cap is cached per kernel form (the probe loop switches to the queue form once
     // the table grows past 2^27 slots, whose occupancy differs from the rounds form's).
-    u32 expand_grid_cap(bool nopf = false) {
-        const int form = nopf ? 2 : probe_loop() < 0 ? 1 : 0;
+    // The dynamic-chunk instantiations (deep levels) have a cap of their own, from their own occupancy
+    // (their registers need not match the static form's).
+    u32 expand_grid_cap(bool nopf = false, bool deep = false) {
+        const int form = (nopf ? 2 : probe_loop() < 0 ? 1 : 0) + (deep && !nopf ? 3 : 0);
         u32& cap = grid_max_[form];
         if (cap) return cap;
         if (grid_env_) return cap = grid_env_;
         int per_cu = 0, cus = 0;
         const size_t dyn = filt_bytes();
         const void* k = form == 1 ? (const void*)expand_fast<M, -4, 0> : (const void*)expand_fast<M, 1, 0>;
+        if (form == 3) k = (const void*)expand_fast<M, 1, 0, false, false, true>;
+        if (form == 4) k = (const void*)expand_fast<M, -4, 0, false, false, true>;
         if constexpr (W >= 4)
             if (nopf) k = (const void*)expand_fast<M, 1, 0, false, true>;
         SR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64 * WPB, dyn));
         SR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o_.device));
         cap = per_cu > 0 && cus > 0 ? (u32)(grid_res_ * per_cu * cus) : ~0u;
-        if (o_.verbose) std::fprintf(stderr, "[sr] expand grid cap %u blocks (%d per CU x %d CUs x %u)%s\n", cap, per_cu, cus, grid_res_, nopf ? " [no prefetch]" : "");
+        if (o_.verbose)
+            std::fprintf(stderr, "[sr] expand grid cap %u blocks (%d per CU x %d CUs x %u)%s\n", cap, per_cu, cus, grid_res_,
+                         nopf ? " [no prefetch]" : form >= 3 ? " [dynamic chunks]" : "");
         return cap;
     }
+    // expand_fast's balanced level geometry (kernels.hpp LevelGeom, the BAL instantiations): for a
+    // pipelined launch (dev_n) whose estimated frontier is at least balance_min_ parents (a smaller
+    // level keeps the fixed geometry and with it the speculative load of its first parents), for a
+    // launch with an exact n at any size; never for the dynamic-chunk form. Counted in
+    // stats.balanced_levels. By default only for one-word states (balance_min_ below).
+    // (The threshold: 2pc N=9's levels 6 and 22, shapes of 37 K and 49 K parents, were 1-2 us slower
+    // balanced, levels of 84 K and more equal or faster: profiles/r07_level_geometry.txt.)
+    bool balance_level(u64 shape, bool dev_n, bool deep) {
+        if (!balance_ || deep || (dev_n ? shape < balance_min_ : balance_min_ == ~0ull)) return false;
+        stats.balanced_levels++;
+        return true;
+    }
+    // The expand_fast instantiation of a launch: counting, wide without prefetch, dynamic chunks (deep)
+    // or static; all but the dynamic chunks with the fixed or the balanced level geometry (bal).
+    template <class L>
+    void launch_form(L& launch, bool nopf, bool deep, bool bal) {
+        if (o_.counters) bal ? launch(expand_fast<M, 1, 0, true, false, false, true>) : launch(expand_fast<M, 1, 0, true>);
+        else if (nopf) launch_nopf(launch, bal);
+        else if (deep) probe_loop() < 0 ? launch(expand_fast<M, -4, 0, false, false, true>) : launch(expand_fast<M, 1, 0, false, false, true>);
+        else if (probe_loop() < 0) bal ? launch(expand_fast<M, -4, 0, false, false, false, true>) : launch(expand_fast<M, -4, 0>);
+        else bal ? launch(expand_fast<M, 1, 0, false, false, false, true>) : launch(expand_fast<M, 1, 0>);
+    }
+    bool balance_ = true;            // SR_BALANCE=0: the fixed geometry everywhere (A/B runs, tests)
+    // SR_BALANCE_MIN. Wider states: no balanced launch unless it is set. The case for equal shares is a
+    // grid of one residency, every workgroup running at once, which only one-word states have (grid_res_).
+    // Wide states take 4-8 parents per wave, so a narrower chunk rounds up to the same parents per wave,
+    // and the lost overlap of the first load cost their latency-bound levels (paxos C=3 0.61-0.63 ->
+    // 0.64-0.65 ms); one of increment_lock N=10's levels of 151 200 parents went from 25 to 39 us.
+    u64 balance_min_ = W == 1 ? (u64)1 << 16 : ~0ull;
     // A level of more than DYN_MIN_RATIO chunks per workgroup takes the kernel with dynamic chunks
     // (kernels.hpp SR_DYN_CHUNKS; the kernel checks the real frontier again). Narrow states only: the
     // wide kernels' registers set their residency.
@@ -1365,8 +1402,10 @@ class Engine final : public EngineBase {
         const u32 ppw_log2 = ppw_env_ >= 0 ? (u32)ppw_env_ : ppw_for(shape);
         const u32 chunks = std::max<u32>(1, blocks_for((shape + (1u << ppw_log2) - 1) >> ppw_log2, WPB));
         const bool nopf = use_nopf(chunks);
-        const u32 grid = std::min(expand_grid_cap(nopf), chunks);
-        const bool deep = deep_level(chunks, grid);
+        u32 grid = std::min(expand_grid_cap(nopf), chunks);
+        const bool deep = !o_.counters && !nopf && deep_level(chunks, grid);
+        if (deep) grid = std::min(expand_grid_cap(false, true), chunks);
+        const bool bal = balance_level(shape, dev_n, deep);
         seq_launch_[sq] = launch_frontier.size();
         // a slotted launch: it counts into its own slot and is published by its successor
         SlotWork sw = slot_work(dev_n);
@@ -1391,11 +1430,7 @@ class Engine final : public EngineBase {
                     m_, arena_.p + fbase * W, 0u, n, view(), arena_.p + nbase * W, apar_.p + nbase, ncap, lc,
                     undiscovered, nullptr, sq, 0u, ppw_log2, filt_arg(), sw);
             };
-            if (o_.counters) launch(expand_fast<M, 1, 0, true>);
-            else if (nopf) launch_nopf(launch);
-            else if (deep) probe_loop() < 0 ? launch(expand_fast<M, -4, 0, false, false, true>) : launch(expand_fast<M, 1, 0, false, false, true>);
-            else if (probe_loop() < 0) launch(expand_fast<M, -4, 0>);
-            else launch(expand_fast<M, 1, 0>);
+            launch_form(launch, nopf, deep, bal);
         }, n);
         slot_seq_ = sq;
         slot_published_ = false;
@@ -1461,7 +1496,10 @@ class Engine final : public EngineBase {
                     const u32 ppw_log2 = ppw_env_ >= 0 ? (u32)ppw_env_ : ppw_for(c);
                     const u32 chunks = std::max<u32>(1, blocks_for((c + (1u << ppw_log2) - 1) >> ppw_log2, WPB));
                     const bool nopf = use_nopf(chunks);
-                    const u32 grid = std::min(expand_grid_cap(nopf), chunks);
+                    u32 grid = std::min(expand_grid_cap(nopf), chunks);
+                    const bool deep = !o_.counters && !nopf && deep_level(chunks, grid);
+                    if (deep) grid = std::min(expand_grid_cap(false, true), chunks);
+                    const bool bal = balance_level(c, false, deep);
                     SlotWork sw{};
                     sw.flags = repair ? SLOT_REPAIR : 0u;
                     if (emask_ && peb) {
@@ -1474,12 +1512,7 @@ class Engine final : public EngineBase {
                                 m_, cur(), ulo, uhi, view(), next, npar, ncap, lc_d_, undiscovered, hcd(sq), sq,
                                 last ? 1u : 0u, ppw_log2, filt_arg(), sw);
                         };
-                        if (o_.counters) launch(expand_fast<M, 1, 0, true>);
-                        else if (nopf) launch_nopf(launch);
-                        else if (deep_level(chunks, grid))
-                            probe_loop() < 0 ? launch(expand_fast<M, -4, 0, false, false, true>) : launch(expand_fast<M, 1, 0, false, false, true>);
-                        else if (probe_loop() < 0) launch(expand_fast<M, -4, 0>);
-                        else launch(expand_fast<M, 1, 0>);
+                        launch_form(launch, nopf, deep, bal);
                     });
                 }
                 return sq;
@@ -1549,7 +1582,7 @@ class Engine final : public EngineBase {
     u32 ppw_for(u64 c) const {
         const double rounds = W >= 4 ? 4.0 : 16.0;
         const double ppw = 64.0 * rounds / en_ratio_;
-        const u32 lmax = W >= 4 ? SR_WIDE_PPW_LOG2_MAX : 6;  // expand_fast's PPW_LOG2_MAX
+        const u32 lmax = expand_ppw_log2_max<M>();  // expand_fast's PPW_LOG2_MAX
         u32 l = 2;
         while (l < lmax && (double)(2u << l) <= ppw) ++l;
         while (l > 2 && ((c + (1u << l) - 1) >> l) < ppw_waves_) --l;
@@ -1584,7 +1617,8 @@ class Engine final : public EngineBase {
     int ppw_env_ = -1;
     bool table_recycle_ = true;  // the visited set is returned zeroed (~Engine)
     u32 grid_res_ = 2;  // residencies per expand grid (set in the constructor)
-    u32 grid_max_[3] = {0, 0, 0};  // cap on expand_fast's grid per form (rounds, queue, wide no-prefetch);
+    u32 grid_max_[5] = {0, 0, 0, 0, 0};  // cap on expand_fast's grid per form (rounds, queue, wide no-prefetch,
+                                   // rounds and queue with dynamic chunks);
                                    // 0 = not computed yet (two device residencies, or SR_GRID_MAX)
     u32 grid_env_ = 0;       // SR_GRID_MAX
     int wide_nopf_ = -1;     // SR_WIDE_NOPF: -1 chosen per level (use_nopf), 0 never, 1 always
@@ -1598,8 +1632,8 @@ class Engine final : public EngineBase {
     int table_kind_ = 0;  // DevicePool memory kind of the visited set (SR_TABLE_KIND, measurement knob)
     // the no-prefetch form exists for wide states only (it is the prefetching kernel otherwise)
     template <class L>
-    void launch_nopf(L& launch) {
-        if constexpr (W >= 4) launch(expand_fast<M, 1, 0, false, true>);
+    void launch_nopf(L& launch, bool bal) {
+        if constexpr (W >= 4) bal ? launch(expand_fast<M, 1, 0, false, true, false, true>) : launch(expand_fast<M, 1, 0, false, true>);
     }
     u64 query_mask_ = 4095;  // spins between hipStreamQuery calls in wait_publish (SR_QUERY_LOG2)
     bool pipeline_ = true;  // FAST-order level pipelining (SR_PIPELINE=0 disables, for A/B runs)

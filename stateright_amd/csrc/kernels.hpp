@@ -36,7 +36,7 @@ constexpr int MAX_PARTS = 64;  // visited-set partitions (one per GPU, or virtua
 #ifndef SR_WIDE_PPW_LOG2_MAX
 #define SR_WIDE_PPW_LOG2_MAX 5
 #endif
-// expand_fast's LDS stage of new narrow states (W < 4), in states per 4 waves (its size sets the
+// expand_fast's LDS stage of new narrow states (W < 4), in states per workgroup (its size sets the
 // blocks per CU; until round 6 it was in 64-bit words, i.e. half as many two-word states).
 #ifndef SR_STAGE_WORDS
 #define SR_STAGE_WORDS 1024
@@ -58,6 +58,11 @@ constexpr u32 DYN_SHARDS = 8;
 #endif
 template <class M>
 constexpr int expand_wpb() { return M::W >= 4 ? 4 : SR_NARROW_WPB; }
+// expand_fast's largest parents per wave (log2). Narrow states: a chunk is 256 parents whatever the
+// waves per workgroup (4 waves of 64, 8 of 32), so the stage, the successor maps and the filter of
+// a workgroup keep their LDS sizes when SR_NARROW_WPB changes.
+template <class M>
+constexpr u32 expand_ppw_log2_max() { return M::W >= 4 ? SR_WIDE_PPW_LOG2_MAX : expand_wpb<M>() >= 8 ? 5 : 6; }
 // ... and for wide states (W >= 4), whose blocks per CU are set by registers, not LDS.
 #ifndef SR_WIDE_STAGE_WORDS
 #define SR_WIDE_STAGE_WORDS 2048
@@ -316,6 +321,34 @@ __device__ __forceinline__ bool filter_seen(u64* filt, bool compact, u32 flog, u
 }
 
 constexpr u32 NO_PARENT = 0xffffffffu;
+
+// How expand_fast's static form cuts the n parents of a level into workgroup shares. Workgroup b
+// of the nblk that expand takes the chunks b, b + nblk, ... of cw parents (cyclic: chunks that run
+// at the same moment stay adjacent in the frontier, and their duplicate probes meet in L2), and
+// wave wid of a chunk at c0 takes the parents [c0 + wid pw, c0 + (wid + 1) pw) below the chunk's end.
+// Fixed geometry: pw = cap parents per wave (the host's ppw_for rule, a power of two) and
+// cw = wpb cap, whatever n is: a level of x chunks per workgroup takes ceil(x) chunk times, and a
+// launch shaped from an estimate above the real frontier leaves workgroups without parents.
+// Balanced geometry (expand_fast's BAL instantiations, chosen by the host per launch; computed on the device from
+// the real n): the fewest rounds r that keep pw <= cap, and the n parents spread evenly over the
+// nblk r chunks, so every workgroup's share is the same to within one chunk width.
+// (nblk wpb cap and nblk r fit 32 bits for every grid the host launches.)
+struct LevelGeom {
+    u32 cw, pw;  // chunk width, parents per wave
+    SR_HD u64 first_chunk(u32 lo, u32 b) const { return lo + (u64)b * cw; }  // workgroup b's first chunk
+    SR_HD u64 stride(u32 nblk) const { return (u64)nblk * cw; }              // ... to its next one
+    SR_HD u64 wave_first(u64 c0, u32 wid) const { return c0 + (u64)wid * pw; }
+    // one past the last parent of the chunk at c0 (wave wid's lane l takes wave_first + l if l < pw
+    // and that rank is below chunk_end)
+    SR_HD u32 chunk_end(u64 c0, u32 hi) const { return c0 + cw < (u64)hi ? (u32)(c0 + cw) : hi; }
+};
+SR_HD LevelGeom level_geometry(u32 n, u32 nblk, u32 wpb, u32 cap, bool balanced) {
+    if (!balanced || n == 0) return LevelGeom{wpb * cap, cap};
+    const u32 per = nblk * wpb * cap;          // parents of one round at the cap
+    const u32 r = (n - 1) / per + 1;           // rounds
+    const u32 cw = (n - 1) / (nblk * r) + 1;   // <= wpb cap
+    return LevelGeom{cw, (cw + wpb - 1) / wpb};
+}
 
 // Per-level device counters. Atomics to one 128-byte line serialise at the coherence point at
 // ~11 ns each whatever the addresses inside it (scripts/microbench_atomics.hip: 12 288 atomics to
@@ -863,22 +896,26 @@ __device__ u64* g_timeline;
 // the kernel's time.
 // Wide states (W >= 4: paxos, the actor models) run three waves per SIMD (<= 168 VGPRs): their
 // levels are latency-bound, and paxos' device-side history search had pushed them to two.
-template <class M, int PB, int POL, bool STATS = false, bool NOPF = false, bool DYN = false>
+// BAL = 1: the balanced level geometry (LevelGeom). A separate instantiation: as a run-time switch its
+// wave-uniform values (the kernel's SGPRs are all in use) spilled 7-20 SGPRs more in every form, and
+// the fixed-geometry forms keep their shifts by a constant (2pc N=9: 1.498-1.502 -> 1.490-1.492 ms).
+template <class M, int PB, int POL, bool STATS = false, bool NOPF = false, bool DYN = false, bool BAL = false>
 __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_waves_per_eu(M::W >= 4 ? SR_WIDE_WAVES : PB < 0 ? 6 : 1))) expand_fast(M m, const u64* __restrict__ frontier, u32 lo, u32 hi,
                                                    TableView t, u64* __restrict__ next, u32* __restrict__ next_par,
                                                    u32 next_cap, LevelCounters* lc, u32 undiscovered,
                                                    HostCounters* hc, u32 seq, u32 reset, u32 ppw_log2,
                                                    u32 filt_log2, SlotWork sw) {
     constexpr int W = M::W, MW = M::MW;
-    // (narrow states: SR_STAGE_WORDS states per 4 waves whatever W; increment_lock's two-word states,
-    // every successor new, flush half as often as with that many words: N=10 3.63 -> 3.32 ms)
-    constexpr int STAGE = W >= 4 ? SR_WIDE_STAGE_WORDS / W : SR_STAGE_WORDS * expand_wpb<M>() / 4;
+    // (narrow states: SR_STAGE_WORDS states per workgroup whatever W and the waves per workgroup, a
+    // chunk being 256 parents either way; increment_lock's two-word states, every successor new,
+    // flush half as often as with that many words: N=10 3.63 -> 3.32 ms)
+    constexpr int STAGE = W >= 4 ? SR_WIDE_STAGE_WORDS / W : SR_STAGE_WORDS;
     extern __shared__ u64 filt[];       // 2^filt_log2 fingerprints (dynamic LDS; 0 = no filter)
     __shared__ u64 stage[STAGE * W];
     __shared__ u32 stage_par[STAGE];
     // Parents per wave at most: wide states (paxos, W = 11) take few parents per wave (ppw_for), and
     // staging 64 of them cost 22.5 KB of LDS per block, which capped residency at 3 blocks per CU.
-    constexpr u32 PPW_LOG2_MAX = W >= 4 ? SR_WIDE_PPW_LOG2_MAX : 6;
+    constexpr u32 PPW_LOG2_MAX = expand_ppw_log2_max<M>();
     constexpr int WPB = expand_wpb<M>();
     __shared__ u64 pst[WPB][(1 << PPW_LOG2_MAX) * W];     // parent states of each wave
     // The wave's successor list, one u16 per successor: parent (bits 0-5) | action << 6, written by
@@ -893,7 +930,8 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
 #ifndef SR_WIDE_MAPCAP
 #define SR_WIDE_MAPCAP 256
 #endif
-    constexpr u32 MAPCAP = W >= 4 ? SR_WIDE_MAPCAP : SR_MAPCAP;
+    // (narrow states: SR_MAPCAP per wave of a 4-wave workgroup, the workgroup's total at 8 waves)
+    constexpr u32 MAPCAP = W >= 4 ? SR_WIDE_MAPCAP : SR_MAPCAP * 4 / expand_wpb<M>();
     static_assert(MW * 64 <= 1024, "action ids must fit 10 bits");
     __shared__ u16 smap[WPB][MAPCAP];
     __shared__ u32 stage_n, base, scratch[2 * WPB];
@@ -933,17 +971,21 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     // Each wave takes ppw = 2^ppw_log2 <= 64 parents (small levels use fewer parents per wave so
     // that their successors spread over more waves: shorter per-lane probe chains). The grid
     // strides over chunks of 4 waves (a pipelined launch is sized from an estimate of the frontier).
+    // The host's ppw is the cap of the balanced geometry (LevelGeom, BAL: the shares are cut from
+    // the real frontier size once it is known; the dynamic chunks keep the fixed geometry).
+    static_assert(!(DYN && BAL), "dynamic chunks keep the fixed geometry");
     ppw_log2 = min(ppw_log2, PPW_LOG2_MAX);
-    const u32 ppw = 1u << ppw_log2;
-    const u64 chunk = (u64)(blockDim.x >> 6) << ppw_log2;
+    constexpr bool balanced = BAL;
+    LevelGeom geom = level_geometry(0, nblk, (u32)WPB, 1u << ppw_log2, false);
     // The wave's first parents. A pipelined launch issues their load before it knows the frontier
     // size (any row below next_cap is inside the arena; rows past the frontier are never used), so
-    // the two round trips overlap instead of following each other.
-    const u64 r_first = lo + (u64)blockIdx.x * chunk + ((u64)wid << ppw_log2) + lane;
+    // the two round trips overlap instead of following each other. (Fixed geometry only: a balanced
+    // launch, a level of many parents, knows its shares after the size.)
+    const u64 r_spec = geom.wave_first(geom.first_chunk(lo, blockIdx.x), (u32)wid) + lane;
     u64 nxt[W];  // the wave's parents of its next chunk (here: its first)
     const bool chained = sw.chain != nullptr;  // (its frontier's offset is read below)
-    const bool spec_first = sw.prev_n && !chained && lane < (int)ppw && r_first < next_cap;
-    if (spec_first) load_state<W>(frontier, r_first, nxt);
+    const bool spec_first = sw.prev_n && !chained && !balanced && lane < (int)geom.pw && r_spec < next_cap;
+    if (spec_first) load_state<W>(frontier, r_spec, nxt);
     if (sw.prev_n) {
         // Pipelined launch (enqueued before the host saw the previous level finish): the frontier
         // is the previous level's claims, and the next level starts right after it. Behind a level
@@ -981,6 +1023,10 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
         lc->unique = sw.ubase + (hi - lo);
     }
     SR_TL(1);
+    if (balanced) geom = level_geometry(hi - lo, nblk, (u32)WPB, 1u << ppw_log2, true);
+    const u32 ppw = geom.pw;    // parents per wave (<= 2^ppw_log2)
+    const u64 chunk = geom.cw;  // parents per chunk
+    const u64 r_first = geom.wave_first(geom.first_chunk(lo, blockIdx.x), (u32)wid) + lane;
     // (the compact filter only for one-word quotient tables: FILT_COMPACT)
     const bool fcompact = M::W == 1 && has_qkey<M>::value && (filt_log2 & FILT_COMPACT) != 0;
     filt_log2 &= FILT_COMPACT - 1;
@@ -994,17 +1040,19 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     u32 succ = 0, enabled = 0, probes = 0, cas = 0;
     // The wave's parents of the next chunk are loaded one chunk ahead: their latency overlaps this
     // chunk's probes instead of stalling the chunk start.
-    const u64 cstride = (u64)nblk * chunk;
-    if (!spec_first && lane < (int)ppw && r_first < hi) load_state<W>(frontier, r_first, nxt);
+    const u64 cstride = geom.stride(nblk);
+    const u64 c_first = geom.first_chunk(lo, blockIdx.x);
+    // (a wave's parents end with its chunk: below hi in the fixed geometry, where wave and chunk end together)
+    const u32 lim_first = BAL ? geom.chunk_end(c_first, hi) : hi;
+    if (!spec_first && lane < (int)ppw && r_first < lim_first) load_state<W>(frontier, r_first, nxt);
     // Wide states without the register prefetch (NOPF: PF false): the first chunk's parents go to
     // the wave's LDS copy here, later chunks load theirs at the chunk start. The W-word prefetch
     // holds 2W VGPRs through every probe round, and a wide kernel's residency is set by its VGPRs
     // (paxos C=3: 146 -> 124 VGPRs, 3 -> 4 blocks per CU). The host takes this form for levels
     // whose chunks all fit the grid (no block strides, so nothing is prefetched anyway).
     constexpr bool PF = W < 4 || !NOPF;
-    const u64 c_first = lo + (u64)blockIdx.x * chunk;
     if constexpr (!PF) {
-        if (lane < (int)ppw && r_first < hi) {
+        if (lane < (int)ppw && r_first < lim_first) {
 #pragma unroll
             for (int i = 0; i < W; ++i) pst[wid][lane * W + i] = nxt[i];
         }
@@ -1029,16 +1077,17 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     u32 kpend = 0;            // (thread 0) the pull in flight
     bool pend = false, first_chunk = true;
     for (u64 c0 = c_first; c0 < hi;) {
-        const u32 wave0 = (u32)(c0 + ((u64)wid << ppw_log2));  // first parent of the wave
+        const u32 wave0 = (u32)geom.wave_first(c0, (u32)wid);  // first parent of the wave
+        const u32 lim = BAL ? geom.chunk_end(c0, hi) : hi;     // its parents end below this rank
         const u32 r = wave0 + lane;
         u32 cnt = 0;
         u64 s[W];
         if constexpr (PF) {
 #pragma unroll
             for (int i = 0; i < W; ++i) s[i] = nxt[i];
-            const u64 rn = c_next + ((u64)wid << ppw_log2) + lane;
-            if (lane < (int)ppw && rn < hi) load_state<W>(frontier, rn, nxt);
-        } else if (c0 != c_first && lane < (int)ppw && r < hi) {
+            const u64 rn = geom.wave_first(c_next, (u32)wid) + lane;
+            if (lane < (int)ppw && rn < (BAL ? geom.chunk_end(c_next, hi) : hi)) load_state<W>(frontier, rn, nxt);
+        } else if (c0 != c_first && lane < (int)ppw && r < lim) {
             load_state<W>(frontier, r, s);  // (the wave's previous parents were last read by its own rounds)
 #pragma unroll
             for (int i = 0; i < W; ++i) pst[wid][lane * W + i] = s[i];
@@ -1055,12 +1104,12 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
             static_assert(MW == 1 && M::ESLOTS <= 64 && 64 % M::ESLOTS == 0, "enabled_slot: ESLOTS must divide 64");
             static_assert(!has_self_loops<M>::value, "enabled_slot: no self_loops hook");
             constexpr u32 ES = M::ESLOTS, PPP = 64 / ES;
-            if (PF && lane < (int)ppw && r < hi) {
+            if (PF && lane < (int)ppw && r < lim) {
 #pragma unroll
                 for (int i = 0; i < W; ++i) pst[wid][lane * W + i] = s[i];
             }
             wave_lds_sync();
-            const u32 np = hi > wave0 ? min(ppw, hi - wave0) : 0u;  // this wave's parents (uniform)
+            const u32 np = lim > wave0 ? min(ppw, lim - wave0) : 0u;  // this wave's parents (uniform)
             u64 mine = 0;
             for (u32 p0 = 0; p0 < np; p0 += PPP) {
                 const u32 p = p0 + (u32)lane / ES, k = (u32)lane % ES;
@@ -1069,7 +1118,7 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                 const u32 i = (u32)lane - p0;
                 if ((u32)lane >= p0 && i < PPP) mine = ES == 64 ? b : (b >> (i * ES)) & ((1ull << (ES % 64)) - 1);
             }
-            if (lane < (int)ppw && r < hi) {
+            if (lane < (int)ppw && r < lim) {
                 mk[0] = mine;
                 cnt = (u32)__popcll(mine);
             }
@@ -1078,7 +1127,7 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
             if (tl_first_chunk) SR_TL(10);
 #endif
         } else
-        if (lane < ppw && r < hi) {
+        if (lane < ppw && r < lim) {
             if constexpr (!PF) {
 #pragma unroll
                 for (int i = 0; i < W; ++i) s[i] = pst[wid][lane * W + i];  // (this lane's own LDS words)
