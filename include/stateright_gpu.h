@@ -67,7 +67,9 @@ enum sr_model_id {
                                      The network of (C, S) holds at most B = C * max(1, 3d + S - 1, 4d)
                                      envelopes, d = S - majority: 8 slots when C, S <= 3 and B <= 8, else
                                      16 (B <= 16), else 32 (states then describe 32 envelopes) */
-    SR_MODEL_SINGLE_COPY = 12     /* (client_count<=6, server_count; <=8 actors) examples/single-copy-register.rs */
+    SR_MODEL_SINGLE_COPY = 12,    /* (client_count<=6, server_count; <=8 actors) examples/single-copy-register.rs */
+    SR_MODEL_LADDER = 13          /* (rungs<=62, free_bits<=57) test fixture: rungs + free_bits action slots,
+                                     (rungs + 1) * 2^free_bits states (stateright_amd/csrc/models.hpp Ladder) */
 };
 
 /* Visit order inside a BFS level. */
@@ -332,6 +334,12 @@ int32_t sr_selftest_level_geometry(void);
  * tester's serialization search on random histories of 1..6 clients.
  * SR_OK or SR_ERR_ARG (sr_last_error says where). */
 int32_t sr_selftest_models(void);
+/* Host-only self-check of 2pc's optional FAST-expansion hooks (models.hpp), N = 1..14 in the
+ * runtime-n form and the compiled-in 9, 10 and 11, over every reachable state for N <= 4 and 10 000
+ * random states per N: `action_masks` gives `apply`'s state for every enabled slot, `enabled_moves`
+ * equals `enabled & ~self_loops` and returns the self-loops' count, every slot it leaves changes the
+ * state (SELF_LOOPS_EXACT); and the same hooks of the Ladder fixture. SR_OK or SR_ERR_ARG. */
+int32_t sr_selftest_action_masks(void);
 /* comm == NULL: `virtual_partitions` partitions in this process on opts->device (same protocol;
  * the partitions store into each other's receive buffers). FAST order only. */
 sr_bfs* sr_gpu_bfs_spawn_partitioned(sr_dist* comm, int32_t virtual_partitions, int32_t model_id,

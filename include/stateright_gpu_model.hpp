@@ -26,6 +26,15 @@
  *                                             generating them. Every slot reported must be a
  *                                             self-loop; an unreported one is still detected
  *                                             (2pc reports all of them: 37% of successors)
+ *             SR_HD enabled_moves(s, out) -> u32   out = enabled & ~self_loops in one pass, returns the
+ *                                             number of self-loops removed (used in their place)
+ *             static constexpr bool SELF_LOOPS_EXACT = true    every slot those leave changes the
+ *                                             state: no successor is compared with its parent
+ *             SR_HD action_masks(a, u64* clr, u64* set)   W == 1: for every enabled slot a,
+ *                                             apply(s, a) = (s & ~clr) | set with masks of the slot
+ *                                             alone; total over slots 0 .. 64 MW - 1. FAST expansion
+ *                                             then looks successors up in a per-wave table (models of
+ *                                             at most 64 slots; SR_ACTION_TABLE=0 keeps apply)
  *             SR_HD canonical(s, out)         a canonical representative under the model's symmetry
  *                                             (the opt-in symmetry_canonical reduction)
  *             SR_HD bool faulted(s)           s lost information when it was built (a state its

@@ -21,6 +21,7 @@ SR_MODEL_PINGPONG = 9
 SR_MODEL_ACTOR_FIXTURE = 10
 SR_MODEL_ABD = 11
 SR_MODEL_SINGLE_COPY = 12
+SR_MODEL_LADDER = 13
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
@@ -167,6 +168,7 @@ SIGNATURES = [
     ("sr_selftest_tables", ctypes.c_int32, []),
     ("sr_selftest_level_geometry", ctypes.c_int32, []),
     ("sr_selftest_models", ctypes.c_int32, []),
+    ("sr_selftest_action_masks", ctypes.c_int32, []),
     ("sr_gpu_bfs_spawn_plugin", _P, [_P, _I64P, ctypes.c_int32, ctypes.POINTER(sr_opts)]),
     ("sr_gpu_bfs_spawn_plugin_partitioned", _P, [_P, _P, ctypes.c_int32, _I64P, ctypes.c_int32,
                                                  ctypes.POINTER(sr_opts)]),

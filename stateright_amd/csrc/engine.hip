@@ -25,6 +25,7 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_BINARY_CLOCK:
         case SR_MODEL_DGRAPH:
         case SR_MODEL_ACTOR_FIXTURE:
+        case SR_MODEL_LADDER:
             return reg_basic(a);
         case SR_MODEL_2PC: return reg_two_phase(a);
         case SR_MODEL_INCREMENT: return reg_increment(a);
@@ -172,6 +173,75 @@ static bool check_self_loops(const M& m, std::string& why) {
                 if (seen.insert(nx).second) queue.push_back(std::move(nx));
             }
         }
+    }
+    return true;
+}
+
+// The FAST expansion's optional hooks of a one-word model against its `enabled`, `self_loops` and
+// `apply` (models.hpp has_action_masks, has_enabled_moves, SELF_LOOPS_EXACT), at one state:
+// `action_masks` gives apply's state for every enabled slot, `enabled_moves` is
+// enabled & ~self_loops with the self-loops' count, and every slot it leaves changes the state.
+template <class M>
+static bool check_action_masks_at(const M& m, u64 s, std::string& why) {
+    static_assert(M::W == 1, "one-word models");
+    constexpr int MW = M::MW;
+    auto fail = [&](const std::string& what) {
+        why = what + " at state " + std::to_string(s);
+        return false;
+    };
+    u64 mk[MW], mv[MW], o[1];
+    m.enabled(&s, mk);
+    u32 loops = 0;
+    for (int w = 0; w < MW; ++w) mv[w] = mk[w];
+    if constexpr (has_self_loops<M>::value) {
+        u64 sl[MW];
+        m.self_loops(&s, mk, sl);
+        for (int w = 0; w < MW; ++w) {
+            loops += (u32)__builtin_popcountll(sl[w]);
+            mv[w] &= ~sl[w];
+        }
+    }
+    if constexpr (has_enabled_moves<M>::value) {
+        u64 em[MW];
+        const u32 r = m.enabled_moves(&s, em);
+        for (int w = 0; w < MW; ++w)
+            if (em[w] != mv[w]) return fail("enabled_moves differs from enabled & ~self_loops in word " + std::to_string(w));
+        if (r != loops) return fail("enabled_moves returns " + std::to_string(r) + " self-loops, self_loops has " + std::to_string(loops));
+    }
+    for (int w = 0; w < MW; ++w)
+        for (u64 bits = mk[w]; bits; bits &= bits - 1) {
+            const int a = w * 64 + __builtin_ctzll(bits);
+            if (!m.apply(&s, a, o)) return fail("apply refuses enabled slot " + std::to_string(a));
+            if constexpr (has_action_masks<M>::value) {
+                u64 clr, set;
+                m.action_masks(a, &clr, &set);
+                if (((s & ~clr) | set) != o[0]) return fail("action_masks of slot " + std::to_string(a) + " differs from apply");
+            }
+            if constexpr (self_loops_exact<M>::value) {
+                if ((mv[w] >> (a & 63) & 1) && o[0] == s) return fail("slot " + std::to_string(a) + " is left enabled and returns the state itself");
+            }
+        }
+    return true;
+}
+// Over every reachable state (walk) and `random` states of `bits` bits.
+template <class M>
+static bool check_action_masks(const M& m, int bits, bool walk, int random, std::string& why) {
+    if (walk) {
+        std::unordered_set<u64> seen;
+        std::vector<u64> queue = init_states_of(m);
+        for (u64 s : queue) seen.insert(s);
+        for (size_t q = 0; q < queue.size(); ++q) {
+            const u64 s = queue[q];
+            if (!check_action_masks_at(m, s, why)) return false;
+            for_each_successor(m, &s, [&](int, const u64* ns) {
+                if (seen.insert(ns[0]).second) queue.push_back(ns[0]);
+            });
+        }
+    }
+    u64 x = 0x9E3779B97F4A7C15ull + (u64)bits;
+    for (int i = 0; i < random; ++i) {
+        x = fmix64(x + 0x632BE59BD9B4E019ull);
+        if (!check_action_masks_at(m, x & ((1ull << bits) - 1), why)) return false;
     }
     return true;
 }
@@ -343,6 +413,10 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             static_cast<act::SingleCopySys&>(m) = act::SingleCopySys::make((int)p[0], np > 1 ? (int)p[1] : 1);
             return f(m);
         }
+        case SR_MODEL_LADDER:
+            need(2);
+            if (p[0] < 1 || p[0] > 62 || p[1] < 0 || p[1] > 57) throw Error(SR_ERR_UNSUPPORTED, "ladder: rungs 1..=62, free bits 0..=57");
+            return f(Ladder{(int)p[0], (int)p[1]});
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -1012,6 +1086,25 @@ int32_t sr_selftest_models(void) {
             return SR_ERR_ARG;
         }
     }
+    return SR_OK;
+}
+
+int32_t sr_selftest_action_masks(void) {
+    std::string why;
+    auto bad = [&](const std::string& who) {
+        set_error(who + ": " + why);
+        return (int32_t)SR_ERR_ARG;
+    };
+    for (int n = 1; n <= 14; ++n) {
+        TwoPhase m;
+        m.n = n;
+        if (!sr::check_action_masks(m, 4 * n + 4, n <= 4, 10000, why)) return bad("2pc n=" + std::to_string(n));
+    }
+    if (!sr::check_action_masks(TwoPhaseT<9>{9}, 40, false, 10000, why)) return bad("2pc n=9 (compiled in)");
+    if (!sr::check_action_masks(TwoPhaseT<10>{10}, 44, false, 10000, why)) return bad("2pc n=10 (compiled in)");
+    if (!sr::check_action_masks(TwoPhaseT<11>{11}, 48, false, 10000, why)) return bad("2pc n=11 (compiled in)");
+    if (!sr::check_action_masks(Ladder{5, 3}, 9, true, 512, why)) return bad("ladder 5+3");
+    if (!sr::check_action_masks(Ladder{58, 8}, 14, false, 10000, why)) return bad("ladder 58+8");
     return SR_OK;
 }
 

@@ -333,6 +333,10 @@ class Engine final : public EngineBase {
         if (const char* e = std::getenv("SR_TABLE_RECYCLE")) table_recycle_ = std::atoi(e) != 0;
         if (const char* e = std::getenv("SR_BALANCE")) balance_ = std::atoi(e) != 0;
         if (const char* e = std::getenv("SR_BALANCE_MIN")) balance_min_ = (u64)std::max(0ll, std::atoll(e));
+        // expand_fast's action table (kernels.hpp ActionTable): a model with `action_masks` whose slots
+        // fit one per lane. SR_ACTION_TABLE=0 keeps `apply` (read per engine: tests run both in one process).
+        action_table_ = action_table_model<M> && A_ <= 64;
+        if (const char* e = std::getenv("SR_ACTION_TABLE")) action_table_ = action_table_ && std::atoi(e) != 0;
     }
     ~Engine() override = default;
 
@@ -1365,6 +1369,7 @@ class Engine final : public EngineBase {
         else if (probe_loop() < 0) bal ? launch(expand_fast<M, -4, 0, false, false, false, true>) : launch(expand_fast<M, -4, 0>);
         else bal ? launch(expand_fast<M, 1, 0, false, false, false, true>) : launch(expand_fast<M, 1, 0>);
     }
+    bool action_table_ = false;      // SLOT_ACTION_TABLE on this engine's expand_fast launches (set in the constructor)
     bool balance_ = true;            // SR_BALANCE=0: the fixed geometry everywhere (A/B runs, tests)
     // SR_BALANCE_MIN. Wider states: no balanced launch unless it is set. The case for equal shares is a
     // grid of one residency, every workgroup running at once, which only one-word states have (grid_res_).
@@ -1409,7 +1414,7 @@ class Engine final : public EngineBase {
         seq_launch_[sq] = launch_frontier.size();
         // a slotted launch: it counts into its own slot and is published by its successor
         SlotWork sw = slot_work(dev_n);
-        sw.flags = flags;
+        sw.flags = flags | (action_table_ ? (u32)SLOT_ACTION_TABLE : 0u);
         sw.arena = arena_.p;
         sw.apar = apar_.p;
         sw.arena_cap = arena_cap_;
@@ -1501,7 +1506,7 @@ class Engine final : public EngineBase {
                     if (deep) grid = std::min(expand_grid_cap(false, true), chunks);
                     const bool bal = balance_level(c, false, deep);
                     SlotWork sw{};
-                    sw.flags = repair ? SLOT_REPAIR : 0u;
+                    sw.flags = (repair ? (u32)SLOT_REPAIR : 0u) | (action_table_ ? (u32)SLOT_ACTION_TABLE : 0u);
                     if (emask_ && peb) {
                         sw.peb = peb;
                         sw.naeb = aeb_.p + nbase;

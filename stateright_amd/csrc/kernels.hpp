@@ -555,6 +555,9 @@ enum SlotFlags : u32 {
     // claimed and appended after the ones the first pass appended; successors are not counted
     // again (the first pass counted every one of them).
     SLOT_REPAIR = 1,
+    // Successors from the wave's action table instead of `apply` (ActionTable below): set by the
+    // host for a model with `action_masks` and at most 64 action slots, unless SR_ACTION_TABLE=0.
+    SLOT_ACTION_TABLE = 2,
 };
 struct SlotWork {
     const u32* prev_n;          // frontier size = the previous level's claims (nullptr: `hi` is exact);
@@ -853,6 +856,37 @@ __device__ __forceinline__ u32 select_bit(u64 m, u32 k) {
     return pos;
 }
 
+// expand_fast's action table for a model with `action_masks` (models.hpp action_table_model): lane a
+// of every wave keeps slot a's (clr, set) pair in four registers, filled once per launch, and a
+// successor lane fetches its slot's pair with ds_bpermute_b32 (one per word that is not zero in
+// every slot: three at 2pc N=9) and forms (s & ~clr) | set. From map entry to successor state that
+// is 13 VALU instructions at 2pc N=9 where the branch-free `apply` (a divide by 5, five 64-bit
+// variable shifts, a dozen selects) took 44 (profiles/r08_instruction_diet.txt). Held in registers
+// because the kernel's LDS has no room for 16-byte entries at six workgroups per CU, and a packed
+// 4- or 8-byte descriptor there would need shifts to decode and an encoding every model's masks
+// must fit (DESIGN.md §3 "Instruction diet"); a table of one
+// slot per lane ends at 64 slots, and a model with more keeps `apply` (the host then leaves
+// SLOT_ACTION_TABLE clear). A cross-lane read returns nothing from an inactive lane, so `next` is
+// called by the whole wave: a lane without a successor passes slot 0 and drops the result.
+template <class M>
+struct ActionTable {
+    static constexpr bool HAS = action_table_model<M>;
+    u32 clr_lo = 0, clr_hi = 0, set_lo = 0, set_hi = 0;
+    __device__ __forceinline__ void fill(const M& m, int lane) {
+        if constexpr (HAS) {
+            u64 c, s;
+            m.action_masks(lane, &c, &s);
+            clr_lo = (u32)c, clr_hi = (u32)(c >> 32), set_lo = (u32)s, set_hi = (u32)(s >> 32);
+        }
+    }
+    __device__ __forceinline__ u64 next(u64 s, u32 slot) const {  // slot < 64, every lane of the wave
+        const int at = (int)(slot << 2);
+        const u32 cl = (u32)__builtin_amdgcn_ds_bpermute(at, (int)clr_lo), ch = (u32)__builtin_amdgcn_ds_bpermute(at, (int)clr_hi);
+        const u32 sl = (u32)__builtin_amdgcn_ds_bpermute(at, (int)set_lo), sh = (u32)__builtin_amdgcn_ds_bpermute(at, (int)set_hi);
+        return (s & ~((u64)ch << 32 | cl)) | ((u64)sh << 32 | sl);
+    }
+};
+
 // Diagnostic build only (SR_TIMELINE=1, scripts/build_timeline.sh): expand_fast's lane 0 of wave 0
 // stamps s_memrealtime (a 100 MHz clock shared by every CU) at each link of its workgroup's chain
 // of dependent round trips, after draining its memory counters, into g_timeline[launch seq % 64]
@@ -968,6 +1002,10 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
         return;
     }
     const u32 nblk = gridDim.x - (svc ? 1u : 0u);  // workgroups that expand parents
+    // successors from the wave's action table (wave-uniform; false for a model without action_masks)
+    const bool tbl = ActionTable<M>::HAS && (sw.flags & SLOT_ACTION_TABLE) != 0;
+    ActionTable<M> atab;
+    if (tbl) atab.fill(m, lane);
     // Each wave takes ppw = 2^ppw_log2 <= 64 parents (small levels use fewer parents per wave so
     // that their successors spread over more waves: shorter per-lane probe chains). The grid
     // strides over chunks of 4 waves (a pipelined launch is sized from an estimate of the frontier).
@@ -1132,11 +1170,16 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
 #pragma unroll
                 for (int i = 0; i < W; ++i) s[i] = pst[wid][lane * W + i];  // (this lane's own LDS words)
             }
-            m.enabled(s, mk);
+            if constexpr (has_enabled_moves<M>::value) {
+                // the enabled mask without its self-loops in one pass; they are counted, never generated
+                succ += m.enabled_moves(s, mk);
+            } else {
+                m.enabled(s, mk);
+            }
 #if SR_TIMELINE
             if (tl_first_chunk) SR_TL(2);
 #endif
-            if constexpr (has_self_loops<M>::value) {
+            if constexpr (has_self_loops<M>::value && !has_enabled_moves<M>::value) {
                 // self-loops are counted here and never generated (has_self_loops)
                 u64 sl[MW];
                 m.self_loops(s, mk, sl);
@@ -1262,16 +1305,30 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                     if (!FP_ONLY) kh[FP_ONLY ? 0 : r] = 0;
                     kt[r] = 0;
                     const u32 i = s0 + (u32)r * 64u + (u32)lane;
+                    // the successor from the action table, fetched by the whole wave (a lane past the
+                    // window's end reads parent 0 and slot 0, and drops the result)
+                    u32 te = 0;
+                    u64 tp = 0, tq = 0;
+                    if (tbl) {
+                        te = i < wend ? smap[wid][i - w0] : 0u;
+                        tp = pst[wid][(te & 63) * W];
+                        tq = atab.next(tp, te >> 6);
+                    }
                     if (i < wend) {
-                        const u32 e = smap[wid][i - w0];
-                        const u32 p = e & 63, a = e >> 6;
                         u64 ps[W], q[W];
+                        bool ok = true;
+                        if (tbl) {
+                            ps[0] = tp, q[0] = tq;
+                        } else {
+                            const u32 e = smap[wid][i - w0];
+                            const u32 p = e & 63, a = e >> 6;
 #pragma unroll
-                        for (int x = 0; x < W; ++x) ps[x] = pst[wid][p * W + x];
-                        bool ok = m.apply(ps, (int)a, q);
+                            for (int x = 0; x < W; ++x) ps[x] = pst[wid][p * W + x];
+                            ok = m.apply(ps, (int)a, q);
+                        }
                         if (ok) {
                             ++succ;  // within boundary: counted once, whatever follows
-                            ok = !same_state<W>(q, ps);  // self-loop: never probed
+                            if constexpr (!exact_moves_model<M>) ok = !same_state<W>(q, ps);  // self-loop: never probed
                         }
                         if (ok) {
                             const ProbeKey k = probe_key(m, t, q);
@@ -1343,7 +1400,13 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                     const bool nw = nmask >> r & 1;
                     u64 q[W];
                     u32 p = 0;
-                    if (nw) {
+                    if (tbl) {
+                        if (__ballot(nw)) {  // (the whole wave fetches, or none of it)
+                            const u32 e = nw ? smap[wid][s0 + (u32)r * 64u + (u32)lane - w0] : 0u;
+                            p = e & 63;
+                            q[0] = atab.next(pst[wid][p * W], e >> 6);
+                        }
+                    } else if (nw) {
                         const u32 e = smap[wid][s0 + (u32)r * 64u + (u32)lane - w0];
                         p = e & 63;
                         u64 ps[W];
@@ -1365,7 +1428,20 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                 const u32 i = it + j * 64 + lane;
                 ok[j] = i < wend;
                 par[j] = 0;
-                if (ok[j]) {
+                if (tbl) {
+                    // the successor from the action table, fetched by the whole wave (a lane past
+                    // the window's end reads parent 0 and slot 0, and drops the result)
+                    const u32 e = ok[j] ? smap[wid][i - w0] : 0u;
+                    par[j] = e & 63;
+                    const u64 ps0 = pst[wid][par[j] * W];
+                    ns[j][0] = atab.next(ps0, e >> 6);
+                    if constexpr (!exact_moves_model<M>) {
+                        if (ok[j] && ns[j][0] == ps0) {  // self-loop: counted, never probed
+                            ++succ;
+                            ok[j] = false;
+                        }
+                    }
+                } else if (ok[j]) {
                     const u32 e = smap[wid][i - w0];
                     const u32 p = e & 63, a = e >> 6;
                     u64 ps[W];
@@ -1373,9 +1449,11 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                     for (int x = 0; x < W; ++x) ps[x] = pst[wid][p * W + x];
                     ok[j] = m.apply(ps, (int)a, ns[j]);
                     par[j] = p;
-                    if (ok[j] && same_state<W>(ns[j], ps)) {  // self-loop: counted, never probed
-                        ++succ;
-                        ok[j] = false;
+                    if constexpr (!exact_moves_model<M>) {
+                        if (ok[j] && same_state<W>(ns[j], ps)) {  // self-loop: counted, never probed
+                            ++succ;
+                            ok[j] = false;
+                        }
                     }
                 }
                 pk[j] = ok[j] ? probe_key(m, t, ns[j]) : ProbeKey{0, 0};

@@ -73,6 +73,35 @@ template <class M>
 struct has_self_loops<M, std::void_t<decltype(std::declval<const M&>().self_loops((const u64*)nullptr, (const u64*)nullptr,
                                                                                   (u64*)nullptr))>> : std::true_type {};
 
+// One-word models (W == 1) whose actions write fields that depend on the slot alone
+// (`action_masks(slot, &clr, &set)`): for every state s and every slot enabled in s, `apply(s, slot)`
+// returns true with o[0] == (s[0] & ~clr) | set. The FAST expansion then keeps one (clr, set) pair
+// per lane, slot = lane, and a successor lane fetches its slot's pair from that lane instead of
+// running `apply` (kernels.hpp ActionTable). The hook is called for every slot below 64 MW, enabled
+// anywhere or not, so it must be total there (its result for a slot that is never enabled is unused).
+template <class M, class = void>
+struct has_action_masks : std::false_type {};
+template <class M>
+struct has_action_masks<M, std::void_t<decltype(std::declval<const M&>().action_masks(0, (u64*)nullptr, (u64*)nullptr))>>
+    : std::true_type {};
+
+// Models that compute their enabled mask without their self-loops in one pass
+// (`enabled_moves(s, mk)`: mk = enabled(s) & ~self_loops(s), returns the number of self-loops
+// removed). The FAST expansion calls it in place of the `enabled` + `self_loops` pair.
+template <class M, class = void>
+struct has_enabled_moves : std::false_type {};
+template <class M>
+struct has_enabled_moves<M, std::void_t<decltype(std::declval<const M&>().enabled_moves((const u64*)nullptr, (u64*)nullptr))>>
+    : std::true_type {};
+
+// Models whose self-loop hook is exact (`static constexpr bool SELF_LOOPS_EXACT = true`): every
+// slot that `enabled_moves` (or `enabled & ~self_loops`) leaves changes the state, so the FAST
+// expansion does not compare a successor with its parent again.
+template <class M, class = void>
+struct self_loops_exact : std::false_type {};
+template <class M>
+struct self_loops_exact<M, std::void_t<decltype(M::SELF_LOOPS_EXACT)>> : std::integral_constant<bool, M::SELF_LOOPS_EXACT> {};
+
 // Wide models whose enabled mask is a per-slot test (`enabled_slot(s, k)` = bit k of `enabled(s)`,
 // `ESLOTS` = max_actions, a power of two <= 64, MW = 1). Small levels of such a model are chains of
 // dependent instructions on a few lanes; the FAST expansion then evaluates the mask with one lane
@@ -261,6 +290,14 @@ struct is_evbits : std::false_type {};
 template <class M>
 struct is_evbits<EvBits<M>> : std::true_type {};
 
+// Canon<M> and EvBits<M> inherit their model's hooks but replace its `apply` (the canonical
+// representative, the extra word), so what `action_masks` and SELF_LOOPS_EXACT say about the
+// model's own successors does not hold for theirs: those two are taken from unwrapped models only.
+template <class M>
+constexpr bool action_table_model = M::W == 1 && has_action_masks<M>::value && !is_canon<M>::value && !is_evbits<M>::value;
+template <class M>
+constexpr bool exact_moves_model = self_loops_exact<M>::value && !is_canon<M>::value && !is_evbits<M>::value;
+
 SR_HD u64 getb(const u64* s, int off, int width) {
     // bit field [off, off+width) of a little-endian multi-word state; width <= 8, no word crossing
     return (s[off >> 6] >> (off & 63)) & ((1ull << width) - 1);
@@ -444,6 +481,71 @@ struct TwoPhaseT {
         o[0] = ((s & ~fmask) | ((fval << fpos) & fmask)) | ebit;
         return true;
     }
+    // The same table as masks of the slot alone (has_action_masks): apply(s, a) = (s & ~clr) | set.
+    // Total over the slots past max_actions (their shifts wrap; nothing enables them).
+    SR_HD void action_masks(int a, u64* clr, u64* set) const {
+        const int n = N();
+        const bool tm = a < 2;
+        const u32 b = tm ? 0u : (u32)(a - 2), rm = b / 5, k = b - 5 * rm;
+        const u32 fpos = (tm ? 2u * n : 2u * rm) & 63;
+        const u64 fval = tm ? (u64)(a + 1) : k == 1 ? 1ull : k == 3 ? 2ull : 3ull;
+        const u64 fmask = (tm || k != 0) ? 3ull << fpos : 0ull;
+        const u32 epos = (tm ? 4u * n + 2 + (u32)a : (k == 0 ? 2u * n + 2 : 3u * n + 2) + rm) & 63;
+        const u64 ebit = (tm || k <= 1) ? 1ull << epos : 0ull;
+        *clr = fmask;
+        *set = ((fval << fpos) & fmask) | ebit;
+    }
+    // No slot that enabled_moves (or enabled & ~self_loops) leaves returns the state itself: see
+    // self_loops above (sr_selftest_action_masks checks it over reachable and random states).
+    static constexpr bool SELF_LOOPS_EXACT = true;
+    // Six fields of a word to stride 5 (field i to bit 5i), three shift-and-mask steps like
+    // working()'s compression: 2-bit fields at stride 2 (bits 0..11), 1-bit fields at stride 1.
+    SR_HD static u32 spread2to5(u32 x) {
+        x = (x | x << 12) & 0x00F000FFu;
+        x = (x | x << 6) & 0x00F03C0Fu;
+        x = (x | x << 3) & 0x06318C63u;
+        return x;
+    }
+    SR_HD static u32 spread1to5(u32 x) {
+        x = (x | x << 16) & 0x0030000Fu;
+        x = (x | x << 8) & 0x00300C03u;
+        x = (x | x << 4) & 0x02108421u;
+        return x;
+    }
+    // enabled(s) & ~self_loops(s) in one pass (has_enabled_moves), the self-loops counted. The fields
+    // are extracted once and the 5-bit groups are built bit-parallel, six rms (30 slots) at a time:
+    // per rm the group is {TmRcvPrepared not yet recorded, Working, Working, Commit sent and not
+    // Committed, Abort sent and not Aborted}.
+    SR_HD u32 enabled_moves(const u64* sp, u64* m) const {
+        const int n = N();
+        const u64 s = sp[0];
+        const u32 rmk = (u32)rmask(), ev = (u32)even_mask();
+        const bool tm0 = ((s >> (2 * n)) & 3) == 0;
+        const u32 prepared = (u32)(s >> (2 * n + 2)) & rmk;
+        const u32 msgp = (u32)(s >> (3 * n + 2)) & rmk;
+        const bool commit = (s >> (4 * n + 2)) & 1, abort = (s >> (4 * n + 3)) & 1;
+        const u32 lo = (u32)s & ev, hi = (u32)(s >> 1) & ev;  // rm_state bits, one rm per even bit
+        const u32 work = ~(hi | lo) & ev, is2 = hi & ~lo, is3 = hi & lo;
+        const u32 rcv = tm0 ? msgp : 0u;
+        const u32 sl0 = rcv & prepared, sl3 = commit ? is2 : 0u, sl4 = abort ? is3 : 0u;  // the self-loops
+        const u32 a0 = rcv & ~prepared;                                 // stride 1
+        const u32 a13 = work | (commit ? (ev & ~is2) << 1 : 0u);        // stride 2: Working | RmRcvCommitMsg << 1
+        const u32 a4 = abort ? ev & ~is3 : 0u;                          // stride 2
+        u64 mlo = (u64)(tm0 && prepared == rmk) | (u64)tm0 << 1, mhi = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (6 * k >= n) break;
+            const u32 w13 = spread2to5((a13 >> (12 * k)) & 0xfffu);
+            const u32 g = spread1to5((a0 >> (6 * k)) & 0x3fu) | (w13 & 0x02108421u) << 1 | w13 << 2 |
+                          spread2to5((a4 >> (12 * k)) & 0x555u) << 4;
+            const int b = 2 + 30 * k;  // the group's first slot
+            mlo |= (u64)g << b;
+            if (b + 30 > 64) mhi |= (u64)(g >> (64 - b));
+        }
+        m[0] = mlo;
+        m[1] = mhi;
+        return (u32)(__builtin_popcount(sl0) + __builtin_popcount(sl3) + __builtin_popcount(sl4));
+    }
     // rm_state fields, bit-parallel: bit 2rm of `ab` is set iff rm is Aborted (3), of `cm` iff
     // Committed (2) (the loop over the rms ran once per property for every new state).
     SR_HD u64 even_mask() const { return 0x5555555555555555ull & ((1ull << (2 * N())) - 1); }
@@ -519,6 +621,54 @@ struct TwoPhaseT {
     }
 };
 using TwoPhase = TwoPhaseT<0>;
+
+// -----------------------------------------------------------------------------------------------
+// Ladder(K, F): a test fixture (no reference counterpart) for models with `action_masks` whose slot
+// count passes 64, where a table held one slot per lane and a one-word mask both end. K rungs are
+// climbed in order and F free bits are set in any order: (K + 1) * 2^F states, depth K + F.
+//   [0,6)    rung   0..K (K <= 62)
+//   [6,6+F)  free bits
+// Slot k < K: enabled iff rung == k; rung <- k + 1. Slot K + j: enabled iff free bit j is clear;
+// sets it. (One bit per rung, slot k setting bit k, would need K + F = 66 bits at the 66 slots of
+// K = 58, F = 8; a one-word state has 63. The rung counter also makes the table clear a field.)
+// -----------------------------------------------------------------------------------------------
+struct Ladder {
+    static constexpr int W = 1, MW = 2, NPROPS = 1;
+    int k, f;  // K <= 62, F <= 57, K + F <= 128
+    int max_actions() const { return k + f; }
+    int max_out_degree() const { return 1 + f; }
+    SR_HD void enabled(const u64* sp, u64* m) const {
+        const u64 s = sp[0];
+        const u32 rung = (u32)(s & 63);
+        const u64 fr = ~(s >> 6) & ((1ull << f) - 1);  // the free bits still clear
+        unsigned __int128 e = (unsigned __int128)fr << k;
+        if (rung < (u32)k) e |= (unsigned __int128)1 << rung;
+        m[0] = (u64)e;
+        m[1] = (u64)(e >> 64);
+    }
+    SR_HD bool apply(const u64* sp, int a, u64* o) const {
+        const u64 s = sp[0];
+        o[0] = a < k ? (s & ~63ull) | (u64)(a + 1) : s | 1ull << (6 + a - k);
+        return true;
+    }
+    SR_HD void action_masks(int a, u64* clr, u64* set) const {
+        *clr = a < k ? 63ull : 0ull;
+        *set = a < k ? (u64)(a + 1) : 1ull << ((6 + a - k) & 63);
+    }
+    static constexpr bool SELF_LOOPS_EXACT = true;  // every enabled slot changes the state
+    SR_HD bool discovers(int, const u64* sp) const { return (sp[0] & 63) > (u64)k; }  // always "on the ladder"
+    int init_states(u64* out) const { out[0] = 0; return 1; }
+    int expectation(int) const { return ALWAYS; }
+    const char* prop_name(int) const { return "on the ladder"; }
+    int describe_width() const { return 2; }
+    void describe(const u64* s, i64* d) const { d[0] = (i64)(s[0] & 63); d[1] = (i64)(s[0] >> 6); }
+    void undescribe(const i64* d, u64* s) const { s[0] = ((u64)d[0] & 63) | (u64)d[1] << 6; }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return k + f; }
+    std::string action_name(i64 id) const {
+        return id < k ? "Climb(" + std::to_string(id) + ")" : "Set(" + std::to_string(id - k) + ")";
+    }
+};
 
 // -----------------------------------------------------------------------------------------------
 // Increment (examples/increment.rs:109-197), n <= 15 threads: i (4 bits) then per thread

@@ -1,4 +1,5 @@
-// Registry family: LinearEquation, BinaryClock, DGraph and the one-actor fixtures (registry.hpp).
+// Registry family: LinearEquation, BinaryClock, DGraph, the one-actor fixtures and the Ladder fixture
+// (registry.hpp).
 #include "registry.hpp"
 #include "dgraph.hpp"
 #include "actor.hpp"
@@ -20,6 +21,12 @@ std::unique_ptr<EngineBase> reg_basic(const EngineArgs& a) {
             ActorFixture m;
             m.kind = (int)p[0];
             return make_for(m, a);
+        }
+        case SR_MODEL_LADDER: {
+            a.need(2);
+            if (p[0] < 1 || p[0] > 62 || p[1] < 0 || p[1] > 57)
+                throw Error(SR_ERR_UNSUPPORTED, "ladder: 1 <= rungs <= 62 and 0 <= free bits <= 57");
+            return make_for(Ladder{(int)p[0], (int)p[1]}, a);
         }
     }
     return nullptr;

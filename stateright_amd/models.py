@@ -180,6 +180,19 @@ class ActorFixture(_Model):
         return [self.kind]
 
 
+class Ladder(_Model):
+    """Test fixture without a reference counterpart (csrc/models.hpp `Ladder`): `rungs` steps climbed
+    in order and `free_bits` bits set in any order, one action slot each, so the slot count can pass
+    64; (rungs + 1) * 2**free_bits states."""
+    MODEL_ID = N.SR_MODEL_LADDER
+
+    def __init__(self, rungs, free_bits):
+        self.rungs, self.free_bits = rungs, free_bits
+
+    def params(self):
+        return [self.rungs, self.free_bits]
+
+
 class SingleCopyRegister(_Model):
     """The single-copy register `SingleCopyModelCfg { client_count, server_count }.into_model()`
     (examples/single-copy-register.rs:40-78): SingleCopyActor servers (a register value each, no
