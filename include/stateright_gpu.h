@@ -68,8 +68,13 @@ enum sr_model_id {
                                      envelopes, d = S - majority: 8 slots when C, S <= 3 and B <= 8, else
                                      16 (B <= 16), else 32 (states then describe 32 envelopes) */
     SR_MODEL_SINGLE_COPY = 12,    /* (client_count<=6, server_count; <=8 actors) examples/single-copy-register.rs */
-    SR_MODEL_LADDER = 13          /* (rungs<=62, free_bits<=57) test fixture: rungs + free_bits action slots,
+    SR_MODEL_LADDER = 13,         /* (rungs<=62, free_bits<=57) test fixture: rungs + free_bits action slots,
                                      (rungs + 1) * 2^free_bits states (stateright_amd/csrc/models.hpp Ladder) */
+    SR_MODEL_SPREAD = 14          /* (words: 1, 2 or 4; key_bits: free_bits < key_bits <= min(64 words, 128);
+                                     free_bits<=24; loops<=4; mark < 2^free_bits) test fixture: the subsets of
+                                     free_bits bits packed into a pseudo-random key of key_bits bits, so the
+                                     visited set's slot encoding is a parameter; 2^free_bits states, `loops`
+                                     unreported self-loops per state (stateright_amd/csrc/models.hpp Spread) */
 };
 
 /* Visit order inside a BFS level. */
@@ -151,7 +156,11 @@ typedef struct sr_stats {
                                     (a projection most actions keep), 0 = by fingerprint          */
     uint32_t balanced_levels;    /* FAST order: expand launches that cut their level into equal
                                     workgroup shares from the real frontier size (SR_BALANCE=0: 0) */
-    uint32_t reserved0;          /* (keeps the size a multiple of 8) */
+    uint32_t table_encoding;     /* the final visited set's slot encoding and the duplicate filter the
+                                    check ran with: bits 0-7 remainder bits (0: fingerprint mode),
+                                    bit 8 4-byte slots, bits 16-23 log2 of the filter's entries (0: no
+                                    filter), bit 24 compact (4-byte) filter entries (this field was
+                                    reserved0 and always 0 before)                                 */
 } sr_stats;
 
 typedef struct sr_bfs sr_bfs;
@@ -340,6 +349,21 @@ int32_t sr_selftest_models(void);
  * equals `enabled & ~self_loops` and returns the self-loops' count, every slot it leaves changes the
  * state (SELF_LOOPS_EXACT); and the same hooks of the Ladder fixture. SR_OK or SR_ERR_ARG. */
 int32_t sr_selftest_action_masks(void);
+/* Host-only self-test of the visited set's encodings as the engine chooses them (kernels.hpp
+ * make_table_view), through growth: for models of 1, 2 and 4 words and every key width, the views of
+ * the tables from the model's smallest (at least 2^10 slots) up to 2^40. Per view, over some thousands of random keys:
+ * the home slot is inside the table, the slot value at the first and the last displacement fits the
+ * slot and decodes to the permuted key, and the duplicate filter's key is injective where the filter
+ * is on. Per growth by 2, 8 and 64: the rehashed slot of every key is the slot a fresh probe finds,
+ * the range-by-range rehash is chosen only where new home >> lg is the old home, and the mode
+ * (quotient or fingerprint) does not change. Allocates nothing. SR_OK or SR_ERR_ARG (sr_last_error). */
+int32_t sr_selftest_table_growth(void);
+/* Host-only: the encoding the engine gives a model of `words` (1, 2 or 4) words with a packed key of
+ * `key_bits` bits in a table of `slots` (a power of two) slots. out[8]: remainder bits (0:
+ * fingerprint mode), displacement bits, key bits, probe limit, 1 for 4-byte slots, duplicate filter
+ * (0 none, 1 8-byte entries, 2 compact 4-byte entries), log2 of its entries, log2 of the model's
+ * smallest table. SR_ERR_ARG for a table below the model's smallest. */
+int32_t sr_table_encoding(int32_t words, int32_t key_bits, uint64_t slots, uint32_t* out);
 /* comm == NULL: `virtual_partitions` partitions in this process on opts->device (same protocol;
  * the partitions store into each other's receive buffers). FAST order only. */
 sr_bfs* sr_gpu_bfs_spawn_partitioned(sr_dist* comm, int32_t virtual_partitions, int32_t model_id,

@@ -63,6 +63,67 @@ def bfs(init_states, actions, next_state, properties, within_boundary=lambda s: 
             "discoveries": {n: path(s) for n, s in discoveries.items()}}
 
 
+# ---- the Spread fixture (stateright_amd/csrc/models.hpp Spread), restated independently ----
+M64 = (1 << 64) - 1
+
+
+def fmix64(k):
+    """murmur3's 64-bit finalizer."""
+    k ^= k >> 33
+    k = (k * 0xff51afd7ed558ccd) & M64
+    k ^= k >> 33
+    k = (k * 0xc4ceb9fe1a85ec53) & M64
+    k ^= k >> 33
+    return k
+
+
+def spread_chunk(x, c):
+    return fmix64((x + 0x9E3779B97F4A7C15 * (2 * c + 1)) & M64)
+
+
+def spread_words(words, key_bits, free_bits, x):
+    """The packed state of the subset x: key = (x | filler << free_bits) mod 2^key_bits in words 0
+    and 1 (little-endian), filler chunks 2 and 3 in words 2 and 3 of a four-word state."""
+    fill = spread_chunk(x, 0) | spread_chunk(x, 1) << 64
+    key = (x | fill << free_bits) & ((1 << key_bits) - 1)
+    out = [key & M64, key >> 64, spread_chunk(x, 2), spread_chunk(x, 3)]
+    return tuple(out[:words])
+
+
+def spread_describe(words, key_bits, free_bits, x):
+    """x, then the low and the high 32 bits of every word."""
+    d = [x]
+    for w in spread_words(words, key_bits, free_bits, x):
+        d += [w & 0xffffffff, w >> 32]
+    return tuple(d)
+
+
+def spread_bfs(words, key_bits, free_bits, loops=0, mark=0):
+    """Spread(words, key_bits, free_bits, loops, mark) on bfs(): states are described states
+    (spread_describe); action j < free_bits sets bit j of x where it is clear, actions free_bits ..
+    free_bits + loops - 1 return the state itself. always "in range" (x < 2^free_bits), sometimes
+    "marked" (x == mark). Adds `actions`: per discovery, the action ids along its path."""
+    assert words in (1, 2, 4) and free_bits < key_bits <= min(64 * words, 128) and 0 <= loops <= 4
+    packed = {}
+
+    def d(x):  # (two subsets never pack alike: x is the key's low bits)
+        if x not in packed:
+            packed[x] = spread_describe(words, key_bits, free_bits, x)
+        return packed[x]
+
+    def actions(s):
+        return [j for j in range(free_bits) if not s[0] >> j & 1] + [free_bits + j for j in range(loops)]
+
+    def next_state(s, a):
+        return d(s[0] | 1 << a) if a < free_bits else s
+
+    r = bfs([d(0)], actions, next_state,
+            [("in range", ALWAYS, lambda s: s[0] < 1 << free_bits), ("marked", SOMETIMES, lambda s: s[0] == mark)])
+    r["actions"] = {name: [(b[0] ^ a[0]).bit_length() - 1 for a, b in zip(path, path[1:])]
+                    for name, path in r["discoveries"].items()}
+    return r
+
+
 # ---- the sliding puzzle (src/lib.rs:43-88) ----
 SLIDES = ("Down", "Up", "Right", "Left")
 SOLVED = (0, 1, 2, 3, 4, 5, 6, 7, 8)

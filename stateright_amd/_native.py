@@ -22,6 +22,7 @@ SR_MODEL_ACTOR_FIXTURE = 10
 SR_MODEL_ABD = 11
 SR_MODEL_SINGLE_COPY = 12
 SR_MODEL_LADDER = 13
+SR_MODEL_SPREAD = 14
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
@@ -68,7 +69,7 @@ class sr_stats(ctypes.Structure):
         ("exchange_fallbacks", ctypes.c_uint32),
         ("owner_key", ctypes.c_uint32),
         ("balanced_levels", ctypes.c_uint32),
-        ("reserved0", ctypes.c_uint32),
+        ("table_encoding", ctypes.c_uint32),
     ]
 
     def as_dict(self):
@@ -169,6 +170,8 @@ SIGNATURES = [
     ("sr_selftest_level_geometry", ctypes.c_int32, []),
     ("sr_selftest_models", ctypes.c_int32, []),
     ("sr_selftest_action_masks", ctypes.c_int32, []),
+    ("sr_selftest_table_growth", ctypes.c_int32, []),
+    ("sr_table_encoding", ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     ("sr_gpu_bfs_spawn_plugin", _P, [_P, _I64P, ctypes.c_int32, ctypes.POINTER(sr_opts)]),
     ("sr_gpu_bfs_spawn_plugin_partitioned", _P, [_P, _P, ctypes.c_int32, _I64P, ctypes.c_int32,
                                                  ctypes.POINTER(sr_opts)]),
@@ -236,6 +239,18 @@ def build_digest():
 
 def last_error():
     return load().sr_last_error().decode(errors="replace")
+
+
+def table_encoding(words, key_bits, slots):
+    """What the engine's table rules (csrc/kernels.hpp make_table_view, min_table_cap, filter_exact,
+    filter_compact_ok) give a model of `words` words with a packed key of `key_bits` bits in a table
+    of `slots` slots: dict(qbits, dbits, bbits, plimit, s32, filter (0 none, 1 8-byte entries,
+    2 compact entries), filter_log2, min_cap_log2). Host-only."""
+    out = (ctypes.c_uint32 * 8)()
+    st = load().sr_table_encoding(words, key_bits, slots, out)
+    if st != 0:
+        raise ValueError(f"sr_table_encoding: {last_error()} (status {st})")
+    return dict(zip(("qbits", "dbits", "bbits", "plimit", "s32", "filter", "filter_log2", "min_cap_log2"), out))
 
 
 def runtime_versions():

@@ -15,10 +15,11 @@ ROOT = os.path.dirname(HERE)
 CDIR = os.path.join(HERE, "csrc")
 SRC = os.path.join(CDIR, "engine.hip")
 UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip", "reg_increment_lock.hip",
-         "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip"]
+         "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip",
+         "reg_spread.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
                                                 "dist.hpp", "dist_host.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
-                                                "actor.hpp", "abd_wide.hpp"]]
+                                                "actor.hpp", "abd_wide.hpp", "table_selftest.hpp"]]
 HEADERS = [os.path.join(ROOT, "include", f) for f in ("stateright_gpu.h", "stateright_gpu_model.hpp")]
 OUT = os.path.join(HERE, "libstateright_gpu.so")
 OBJDIR = os.path.join(HERE, "build")

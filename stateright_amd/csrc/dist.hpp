@@ -1529,7 +1529,7 @@ class DistEngine final : public EngineBase {
         while ((1ull << lg) < f) ++lg;
         const u64 S = to0.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
         // range by range as in Engine::launch_rehash (no clear of the new table), else clear + CAS
-        const bool ranges = from.qbits && to0.qbits && from.qbits == to0.qbits + lg && f <= S && p.cap % S == 0;
+        const bool ranges = rehash_by_ranges(from, to0, lg, p.cap);
         p.keys.alloc(o_.device, p.words());
         if (ranges) {
             const u64 nranges = p.cap / S, spill_cap = nranges + 65536;
@@ -1839,6 +1839,7 @@ class DistEngine final : public EngineBase {
         stats.total_sec = secs(t_start, t_end);
         stats.table_capacity = parts_[0].cap * T_;
         stats.displacement_limit = parts_[0].view().plimit;
+        stats.table_encoding = table_encoding_word(parts_[0].view(), filt_log2_, false);
     }
 
     // ---- pipelined level loop ------------------------------------------------------------------
@@ -2556,7 +2557,7 @@ class DistEngine final : public EngineBase {
     DBuf<u64> rows_all_, rows_mine_;  // gathered rows (T x RW) / this rank's row (RCCL mode)
     DistContext* ctx_ = nullptr;      // pooled stream, counters, pinned mirrors, events
     double en_ratio_ = 8.0;  // enabled action slots per parent, last level
-    u32 filt_log2_ = std::getenv("SR_FILTER_LOG2") ? (u32)std::atoi(std::getenv("SR_FILTER_LOG2")) : (W >= 4 ? 10 : 9);
+    u32 filt_log2_ = std::getenv("SR_FILTER_LOG2") ? (u32)std::atoi(std::getenv("SR_FILTER_LOG2")) : default_filter_log2<W>();
 
     // Parents per wave (log2) for a frontier of ~c states (the single-GPU engine's rule,
     // Engine::ppw_for): ~16 successor rounds per wave for 1-2 word states, 4 for wider ones, and

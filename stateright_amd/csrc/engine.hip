@@ -6,6 +6,7 @@
 #include "paxos.hpp"
 #include "abd_wide.hpp"
 #include "dist_host.hpp"
+#include "table_selftest.hpp"
 
 namespace sr {
 
@@ -38,6 +39,7 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_ABD:
         case SR_MODEL_SINGLE_COPY:
             return reg_registers(a);
+        case SR_MODEL_SPREAD: return reg_spread(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
@@ -417,6 +419,8 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             need(2);
             if (p[0] < 1 || p[0] > 62 || p[1] < 0 || p[1] > 57) throw Error(SR_ERR_UNSUPPORTED, "ladder: rungs 1..=62, free bits 0..=57");
             return f(Ladder{(int)p[0], (int)p[1]});
+        case SR_MODEL_SPREAD:
+            return with_spread_model(p, np, [&](const auto& m) -> i64 { return f(m); });
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -936,6 +940,40 @@ int32_t sr_selftest_tables(void) {
     return SR_OK;
 }
 
+int32_t sr_selftest_table_growth(void) {
+    try {
+        std::string why;
+        if (!table_growth_selftest(why)) {
+            set_error(why);
+            return SR_ERR_ARG;
+        }
+        return SR_OK;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int32_t sr_table_encoding(int32_t words, int32_t key_bits, uint64_t slots, uint32_t* out) {
+    try {
+        if (!out || key_bits < 2 || (words != 1 && words != 2 && words != 4) || key_bits > std::min(64 * words, 128) ||
+            !slots || (slots & (slots - 1)))
+            throw Error(SR_ERR_ARG, "sr_table_encoding: words 1, 2 or 4, 2 <= key_bits <= min(64 words, 128), slots a power of two");
+        const TableEncoding e = words == 1   ? table_encoding_of<1>(key_bits, slots)
+                                : words == 2 ? table_encoding_of<2>(key_bits, slots)
+                                             : table_encoding_of<4>(key_bits, slots);
+        const u32 v[8] = {e.qbits, e.dbits, e.bbits, e.plimit, e.s32, e.filter, e.filter_log2, e.min_cap_log2};
+        std::copy(v, v + 8, out);
+        return SR_OK;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
 // expand_fast's level geometry (kernels.hpp LevelGeom / level_geometry) walked on the host the way
 // the kernel walks it: workgroup b from first_chunk in steps of stride while the chunk starts below
 // hi, wave wid's lanes l < pw at wave_first + l below chunk_end. A wave's ranks are an interval, so
@@ -1170,4 +1208,5 @@ extern "C" int64_t sr_timeline_fetch(int32_t device, uint64_t* out, int64_t cap)
 #include "reg_ping_pong.hip"
 #include "reg_registers.hip"
 #include "reg_registers_wide.hip"
+#include "reg_spread.hip"
 #endif

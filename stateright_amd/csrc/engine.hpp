@@ -586,8 +586,7 @@ class Engine final : public EngineBase {
         u32 lg = 0;
         while ((1ull << lg) < f) ++lg;
         const u64 S = to0.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
-        const bool ranges = rehash_ranges_ && !from.meta && from.qbits && to0.qbits &&
-                            from.qbits == to0.qbits + lg && f <= S && cap % S == 0;
+        const bool ranges = rehash_ranges_ && !from.meta && rehash_by_ranges(from, to0, lg, cap);
         alloc_table(cap, !ranges);
         table_unzeroed_ = ranges;
         SR_HIP(hipMemsetAsync(aux_.p, 0, sizeof(u32), stream_));
@@ -667,6 +666,7 @@ class Engine final : public EngineBase {
     void displacement_stats() {
         const TableView v = view();
         stats.displacement_limit = v.plimit;
+        stats.table_encoding = table_encoding_word(v, filt_log2_, filt_compact_);
         if (!o_.counters || !cap_) return;
         if (!aux_.p) aux_.alloc(o_.device, 2);
         SR_HIP(hipMemsetAsync(aux_.p + 1, 0, sizeof(u32), stream_));
@@ -1647,7 +1647,7 @@ class Engine final : public EngineBase {
     u32 slot_seq_ = 0;                // sequence number of the last one
     bool slot_published_ = true;      // its publish is done or enqueued
     std::map<u32, size_t> seq_launch_;  // launch sequence number -> index in launch_frontier
-    u32 filt_log2_ = W >= 4 ? 10 : 9;  // block-local duplicate filter (SR_FILTER_LOG2 sweep in profiles/)
+    u32 filt_log2_ = default_filter_log2<W>();  // block-local duplicate filter
     bool filt_compact_ = false;         // ... in 4-byte entries (kernels.hpp FILT_COMPACT)
     size_t filt_bytes() const { return filt_log2_ ? (size_t)(filt_compact_ ? 4u : 8u) << filt_log2_ : 0u; }
     u32 filt_arg() const { return filt_log2_ | (filt_compact_ ? FILT_COMPACT : 0u); }

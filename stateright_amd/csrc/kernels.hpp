@@ -22,6 +22,8 @@
 #include <cstddef>
 #include <cstdlib>
 
+#include "../../include/stateright_gpu.h"
+#include "device.hpp"
 #include "models.hpp"
 
 namespace sr {
@@ -85,7 +87,8 @@ enum ErrBits { ERR_TABLE_FULL = 1, ERR_FRONTIER_OVERFLOW = 2, ERR_PEER_TIMEOUT =
 //  * fingerprint mode (qbits == 0): a slot holds the 64-bit fingerprint. Exact for one-word states
 //    (fingerprint<1> is a bijection); a 64-bit hash for wider states, like the reference's own
 //    visited set (DashMap keyed by a 64-bit ahash fingerprint, src/checker/bfs.rs:26,245-247).
-//  * quotient mode (qbits > 0, models with a packed key of B = bbits <= 120 bits, `qkey`): the key
+//  * quotient mode (qbits > 0, models with a packed key of B = bbits bits, `qkey`: B <= 62 on one
+//    word, B <= 96 on more, quotient_model): the key
 //    goes through a bijection on B bits (qperm); its top k = log2(cap) bits are the HOME slot and
 //    the slot stores the other qbits = B - k bits (the remainder) above dbits = 64 - qbits bits
 //    holding 1 + the linear-probe displacement from home. A slot value determines the key exactly,
@@ -200,10 +203,10 @@ SR_HD ProbeKey reprobe(const TableView& from, const TableView& to, u64 i, u64 v)
     return from.qbits ? quot_probe(to, quot_decode(from, i, v)) : fp_probe(to, v);
 }
 
-// Host: the view of a table of `cap` (a power of two) slots for model M. Quotient mode whenever
-// the model packs its states into a key (qkey) whose remainder fits a slot with >= 8 displacement
-// bits; min_table_cap keeps every table of such a model in that mode from the start (a
-// fingerprint cannot be turned back into a key when the table grows).
+// Host: the view of a table of `cap` (a power of two) slots for model M. Quotient mode for every
+// table of a model that quotient_model says packs its states into a key (qkey); min_table_cap is
+// the smallest table whose remainder fits a slot with >= 8 displacement bits, and every table of
+// such a model starts there or above.
 // SR_DISP_LIMIT (tests) lowers every table's probe limit, to force the overflow path.
 inline u32 forced_probe_limit() {
     const char* e = std::getenv("SR_DISP_LIMIT");
@@ -220,13 +223,18 @@ inline bool slot32_enabled() {
     return on;
 }
 // Whether model M keys its visited set by its packed key (quotient mode) rather than by a
-// fingerprint; fixed per model instance, since a fingerprint cannot be turned back into a key.
+// fingerprint; fixed per model instance, since a fingerprint cannot be turned back into a key (and
+// a key's slot value not into a fingerprint): make_table_view, min_table_cap and filter_exact all
+// ask here, so every table of a check, at every size it grows to, is in the one mode. Multi-word
+// keys: up to 96 bits, the widest whose smallest quotient table (2^(B - 56) slots, min_table_cap)
+// is 2^40 slots; a wider key is fingerprinted at every size.
+constexpr u32 QUOT_MAX_REMAINDER = 56;  // remainder bits of an 8-byte slot (>= 8 displacement bits)
 template <class M>
 inline bool quotient_model(const M& m) {
     if constexpr (has_qkey<M>::value) {
         const int B = m.qkey_bits();
         if constexpr (M::W == 1) return B >= 2 && B <= 62;
-        else return B <= 120;
+        else return B >= 2 && B <= 96;
     }
     (void)m;
     return false;
@@ -238,21 +246,19 @@ inline TableView make_table_view(const M& m, u64* keys, u64* meta, u64 cap, bool
         const u32 B = (u32)m.qkey_bits();
         u32 k = 0;
         while ((1ull << k) < cap) ++k;
-        if constexpr (M::W == 1) {
-            if (quotient_model(m)) {
-                v.qbits = B > k ? B - k : 1u;
-                v.bbits = B;
-                if (slot32_enabled() && v.qbits + SLOT32_DMIN <= 32) {
-                    v.s32 = 1;
-                    v.dbits = 32 - v.qbits;
-                } else {
-                    v.dbits = 64 - v.qbits;
-                }
-            }
-        } else if (B <= 120 && B > k && B - k <= 56) {
-            v.qbits = B - k;
-            v.dbits = 64 - v.qbits;
+        if (quotient_model(m)) {
+            // a table larger than the key space keeps a 1-bit remainder (its keys are homed in the
+            // first 2^(B-1) slots), for multi-word keys as for one-word ones
+            v.qbits = B > k ? B - k : 1u;
             v.bbits = B;
+            if (v.qbits > QUOT_MAX_REMAINDER)
+                throw Error(SR_ERR_ARG, "make_table_view: a quotient table below min_table_cap");
+            if (M::W == 1 && slot32_enabled() && v.qbits + SLOT32_DMIN <= 32) {
+                v.s32 = 1;
+                v.dbits = 32 - v.qbits;
+            } else {
+                v.dbits = 64 - v.qbits;
+            }
         }
     }
     v.plimit = encoding_probe_limit(v.qbits, v.dbits);
@@ -263,9 +269,9 @@ template <class M>
 inline u64 min_table_cap(const M& m) {
     if constexpr (has_qkey<M>::value) {
         const int B = m.qkey_bits();
-        if (M::W == 1 && quotient_model(m) && B > 56) return 1ull << (B - 56);
-        if (M::W >= 2 && B > 56 && B <= 96) return 1ull << (B - 56);
+        if (quotient_model(m) && B > (int)QUOT_MAX_REMAINDER) return 1ull << (B - (int)QUOT_MAX_REMAINDER);
     }
+    (void)m;
     return 1;
 }
 
@@ -296,19 +302,25 @@ SR_HD u32 filter_index(const TableView& t, u64 fk) { return t.qbits ? (u32)fk : 
 // tables (increment_lock N >= 9: every successor is new, nothing to filter) run without it.
 template <class M>
 inline bool filter_exact(const M& m) {
-    const TableView v = make_table_view(m, nullptr, nullptr, min_table_cap(m), true);
-    return !v.qbits || (M::W == 1 && v.bbits <= 63);
+    return !quotient_model(m) || M::W == 1;  // (a one-word quotient key has at most 62 bits)
 }
 // Compact filter (expand_fast's filt_log2 argument | FILT_COMPACT): 4-byte entries for one-word
 // quotient tables whose filter key fk (<= 2^B) loses at most 30 bits past the entry index: entry
 // fk & (2^L - 1) holds (fk >> L) | 2^31 (never 0, the empty entry), exact for B - L <= 30. Twice the
 // entries in the same LDS (2pc N=9, B = 40: 1024 entries in 4 KB instead of 512).
 constexpr u32 FILT_COMPACT = 0x100;
+// Entries (log2, of 8 bytes) of the filter unless SR_FILTER_LOG2 sets them (SR_FILTER_LOG2 sweep in profiles/).
+template <int W>
+constexpr u32 default_filter_log2() { return W >= 4 ? 10 : 9; }
 template <class M>
 inline bool filter_compact_ok(const M& m, u32 log2_entries) {
     if (M::W != 1 || !filter_exact(m)) return false;
     const TableView v = make_table_view(m, nullptr, nullptr, min_table_cap(m), true);
     return v.qbits && v.bbits <= 30 + log2_entries;
+}
+// sr_stats.table_encoding: what a check ran with (host).
+inline u32 table_encoding_word(const TableView& t, u32 filt_log2, bool compact) {
+    return t.qbits | (t.s32 ? 1u << 8 : 0u) | filt_log2 << 16 | (compact ? 1u << 24 : 0u);
 }
 // The block-local filter's lookup-and-insert of key fk: whether fk was there (a duplicate).
 __device__ __forceinline__ bool filter_seen(u64* filt, bool compact, u32 flog, u32 fmask, const TableView& t, u64 fk) {
@@ -1914,6 +1926,14 @@ constexpr u32 REBUILD_ROWS = 4;
 constexpr u32 REBUILD_BYTES = 32768;
 template <class T>
 constexpr u32 rebuild_slots() { return REBUILD_BYTES / sizeof(T); }
+// Host: whether a table `from` grows by 2^lg into one of `cap` slots with view `to` range by range
+// (rehash_ranges<u32> when to.s32, else <u64>; the slots of `from` may be of the other width, they
+// are read through slot_load): both in quotient mode with lg remainder bits turned into home bits,
+// so that new home >> lg == old home, and whole ranges. Else a clear plus a CAS per entry (rehash).
+inline bool rehash_by_ranges(const TableView& from, const TableView& to, u32 lg, u64 cap) {
+    const u64 S = to.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
+    return from.qbits && to.qbits && from.qbits == to.qbits + lg && (1ull << lg) <= S && cap % S == 0;
+}
 template <class T>
 __global__ void __launch_bounds__(REBUILD_BLOCK)
     rehash_ranges(TableView from, u64 from_cap, TableView to, u32 lg, u64* spill, u64 spill_cap, u32* err) {

@@ -39,9 +39,10 @@ inline u32 model_emask(const M& m) {
     else return 0;
 }
 
-// Models whose states pack into a key of at most 120 bits (`qkey_bits()` and `qkey(s)`: an
-// injective packing of the state into an integer below 2^qkey_bits) can use the exact quotient
-// visited set (kernels.hpp TableView).
+// Models whose states pack into a key (`qkey_bits()` and `qkey(s)`: an injective packing of the
+// state into an integer below 2^qkey_bits) use the exact quotient visited set (kernels.hpp
+// TableView) when the key has at most 62 bits on one word or 96 on more (kernels.hpp
+// quotient_model), and a fingerprint otherwise.
 template <class M, class = void>
 struct has_qkey : std::false_type {};
 template <class M>
@@ -667,6 +668,91 @@ struct Ladder {
     i64 action_id_bound() const { return k + f; }
     std::string action_name(i64 id) const {
         return id < k ? "Climb(" + std::to_string(id) + ")" : "Set(" + std::to_string(id - k) + ")";
+    }
+};
+
+// -----------------------------------------------------------------------------------------------
+// Spread<W>(B, F, loops, mark): a test fixture (no reference counterpart) whose key width is a
+// parameter, so that a check can be put into any slot encoding of the visited set (kernels.hpp
+// make_table_view) whatever its size. A state is a subset x of F free bits, packed into a key of
+// B bits, F < B <= min(64 W, 128):
+//   key = (x | filler(x) << F) mod 2^B, little-endian in words 0 and 1 (word 1 only for W >= 2)
+// filler(x) is 128 bits, 64-bit chunk c being fmix64(x + an odd constant of c): every key bit up
+// to B - 1 is pseudo-random, and the key stays injective because x sits in its low bits. W = 4:
+// words 2 and 3 hold chunks 2 and 3 of the filler, so all four words are loaded, stored and
+// compared (equal x <=> equal words).
+// Slot j < F: enabled iff bit j of x is clear; sets it. Slots F .. F + loops - 1 (loops <= 4) are
+// always enabled and return the state itself, and are NOT reported through `self_loops`.
+// 2^F states, depth F, 1 + F 2^(F-1) + loops 2^F generated; level L holds C(F, L) states, each
+// generated by L parents. always "in range": the words are the packing of their own x (never
+// violated). sometimes "marked": x == mark.
+// -----------------------------------------------------------------------------------------------
+template <int W_>
+struct Spread {
+    static_assert(W_ == 1 || W_ == 2 || W_ == 4, "Spread: 1, 2 or 4 words");
+    static constexpr int W = W_, MW = 1, NPROPS = 2;
+    int b, f, loops;
+    u64 mark;
+    int max_actions() const { return f + loops; }
+    int max_out_degree() const { return f + loops; }
+    SR_HD static u64 chunk(u64 x, int c) { return fmix64(x + 0x9E3779B97F4A7C15ull * (u64)(2 * c + 1)); }
+    SR_HD u64 fmask() const { return (1ull << f) - 1; }
+    SR_HD void pack(u64 x, u64* o) const {
+        const unsigned __int128 fill = (unsigned __int128)chunk(x, 0) | (unsigned __int128)chunk(x, 1) << 64;
+        unsigned __int128 key = (unsigned __int128)x | fill << f;
+        if (b < 128) key &= ((unsigned __int128)1 << b) - 1;
+        o[0] = (u64)key;
+        if constexpr (W_ >= 2) o[1] = (u64)(key >> 64);
+        if constexpr (W_ == 4) {
+            o[2] = chunk(x, 2);
+            o[3] = chunk(x, 3);
+        }
+    }
+    SR_HD void enabled(const u64* s, u64* m) const { m[0] = (~s[0] & fmask()) | ((1ull << loops) - 1) << f; }
+    SR_HD bool apply(const u64* s, int a, u64* o) const {
+        if (a < f) {
+            pack((s[0] & fmask()) | 1ull << a, o);
+        } else {
+#pragma unroll
+            for (int i = 0; i < W_; ++i) o[i] = s[i];
+        }
+        return true;
+    }
+    SR_HD bool discovers(int p, const u64* s) const {
+        const u64 x = s[0] & fmask();
+        if (p == 1) return x == mark;  // sometimes "marked"
+        u64 t[W_];                     // always "in range": discovered at a state that is not pack(x)
+        pack(x, t);
+        bool same = true;
+#pragma unroll
+        for (int i = 0; i < W_; ++i) same &= t[i] == s[i];
+        return !same;
+    }
+    int init_count() const { return 1; }
+    int init_states(u64* out) const { pack(0, out); return 1; }
+    int expectation(int p) const { return p == 0 ? ALWAYS : SOMETIMES; }
+    const char* prop_name(int p) const { return p == 0 ? "in range" : "marked"; }
+    int qkey_bits() const { return b; }
+    SR_HD unsigned __int128 qkey(const u64* s) const {
+        if constexpr (W_ == 1) return s[0];
+        else return (unsigned __int128)s[0] | ((unsigned __int128)s[1] << 64);
+    }
+    // x, then the low and the high 32 bits of every word
+    int describe_width() const { return 1 + 2 * W_; }
+    void describe(const u64* s, i64* d) const {
+        d[0] = (i64)(s[0] & fmask());
+        for (int i = 0; i < W_; ++i) {
+            d[1 + 2 * i] = (i64)(s[i] & 0xffffffffull);
+            d[2 + 2 * i] = (i64)(s[i] >> 32);
+        }
+    }
+    void undescribe(const i64* d, u64* s) const {
+        for (int i = 0; i < W_; ++i) s[i] = ((u64)d[1 + 2 * i] & 0xffffffffull) | (u64)d[2 + 2 * i] << 32;
+    }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return f + loops; }
+    std::string action_name(i64 id) const {
+        return id < f ? "Set(" + std::to_string(id) + ")" : "Loop(" + std::to_string(id - f) + ")";
     }
 };
 

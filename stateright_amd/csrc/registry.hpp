@@ -46,5 +46,23 @@ std::unique_ptr<EngineBase> reg_paxos_wide(const EngineArgs& a);      // paxos, 
 std::unique_ptr<EngineBase> reg_ping_pong(const EngineArgs& a);       // ping-pong
 std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 slots) and the single-copy register
 std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
+std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4)
+
+// The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark), handed
+// to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip) validate alike.
+template <class F>
+auto with_spread_model(const i64* p, int np, F&& f) {
+    if (np < 5) throw Error(SR_ERR_ARG, "spread needs 5 params (words, key_bits, free_bits, loops, mark)");
+    const i64 w = p[0], b = p[1], fb = p[2], loops = p[3], mark = p[4];
+    if (w != 1 && w != 2 && w != 4) throw Error(SR_ERR_UNSUPPORTED, "spread: words must be 1, 2 or 4");
+    if (fb < 1 || fb > 24) throw Error(SR_ERR_UNSUPPORTED, "spread: free_bits must be in 1..=24");
+    if (b <= fb || b > std::min<i64>(64 * w, 128))
+        throw Error(SR_ERR_UNSUPPORTED, "spread: free_bits < key_bits <= min(64 words, 128)");
+    if (loops < 0 || loops > 4) throw Error(SR_ERR_UNSUPPORTED, "spread: loops must be in 0..=4");
+    if (mark < 0 || mark >> fb) throw Error(SR_ERR_ARG, "spread: mark must be below 2^free_bits");
+    if (w == 1) return f(Spread<1>{(int)b, (int)fb, (int)loops, (u64)mark});
+    if (w == 2) return f(Spread<2>{(int)b, (int)fb, (int)loops, (u64)mark});
+    return f(Spread<4>{(int)b, (int)fb, (int)loops, (u64)mark});
+}
 
 }  // namespace sr

@@ -193,6 +193,21 @@ class Ladder(_Model):
         return [self.rungs, self.free_bits]
 
 
+class Spread(_Model):
+    """Test fixture without a reference counterpart (csrc/models.hpp `Spread`): the subsets of
+    `free_bits` bits, packed with pseudo-random filler into a key of `key_bits` bits on `words` (1, 2
+    or 4) words, so the key width, and with it the visited set's slot encoding, is a parameter.
+    2**free_bits states, depth free_bits; `loops` (<= 4) further slots return the state itself without
+    the model reporting them as self-loops; `sometimes "marked"` holds at the subset `mark`."""
+    MODEL_ID = N.SR_MODEL_SPREAD
+
+    def __init__(self, words, key_bits, free_bits, loops=0, mark=0):
+        self.words, self.key_bits, self.free_bits, self.loops, self.mark = words, key_bits, free_bits, loops, mark
+
+    def params(self):
+        return [self.words, self.key_bits, self.free_bits, self.loops, self.mark]
+
+
 class SingleCopyRegister(_Model):
     """The single-copy register `SingleCopyModelCfg { client_count, server_count }.into_model()`
     (examples/single-copy-register.rs:40-78): SingleCopyActor servers (a register value each, no

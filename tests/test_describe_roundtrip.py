@@ -33,6 +33,9 @@ CASES = [
     (N.SR_MODEL_2PC, [5], 8832),                  # examples/2pc.rs:127-134
     (N.SR_MODEL_INCREMENT_LOCK, [4], None),
     (N.SR_MODEL_INCREMENT, [3], None),
+    (N.SR_MODEL_SPREAD, [1, 45, 12, 2, 0], 4096),  # (words, key_bits, free_bits, loops, mark): 2^12 states
+    (N.SR_MODEL_SPREAD, [2, 79, 12, 0, 0], 4096),
+    (N.SR_MODEL_SPREAD, [4, 128, 10, 1, 0], 1024),
 ]
 
 
