@@ -24,6 +24,8 @@
  *                                                                     src/checker/bfs.rs:187-189
  *   sr_gpu_bfs_free               <- Drop of the checker (join(self) consumes it in Rust)
  *   sr_last_error                 <- the reference panics; see "Errors" below
+ *   sr_gpu_sim_spawn / sr_sim_walk <- new: the random-walk simulation checker (upstream's
+ *                                    `spawn_simulation`, added after 0.28); see its section below
  *   sr_dist_* / sr_gpu_bfs_spawn_partitioned <- new: the visited set partitioned over GPUs
  *
  * Models: device code cannot call host function pointers, so `impl Model` becomes a registry of
@@ -243,6 +245,63 @@ int64_t sr_gpu_bfs_visits(const sr_bfs* bfs, int64_t* out, int64_t cap);
  * search gathers every rank's records at join, so its tree is global on every rank. */
 int64_t sr_gpu_bfs_visit_tree(const sr_bfs* bfs, int64_t* parent, int64_t* action, int64_t cap);
 void sr_gpu_bfs_free(sr_bfs* bfs);
+
+/* ---- Random-walk simulation checker (the counterpart of the simulation checker Stateright gained
+ * after 0.28; stateright_amd/csrc/sim.hpp defines the walk, for host and device from one source) ----
+ * `walks` independent random traces run from the init states, one GPU lane per trace; the properties
+ * are evaluated on every state of a trace and NO visited set is kept, so a model whose reachable set
+ * fits no card still gets discoveries. What it does not prove: a run WITHOUT a discovery proves
+ * nothing (sr_gpu_bfs_is_done is 1 only when every property was discovered).
+ *
+ * Determinism: trace w is a pure function of (model, seed, w, max_depth): a counter-based generator
+ * r(seed, w, t, k) (two rounds of murmur3's fmix64 over the seed, the trace index, the step t and
+ * the attempt k) draws the init state and, per step, one of the enabled action slots; a slot whose
+ * next state is None or outside the boundary is cleared and another is drawn; a state where none is
+ * left is terminal. A trace ends there (reason 1), at max_depth steps (2) or at a state past its
+ * model's encoding (3, the check then fails with SR_ERR_UNSUPPORTED as a BFS check does). The
+ * traces run in batches of consecutive indices and the check stops after the first whole batch at
+ * whose end every property is discovered, state_count >= target_state_count, or `walks` traces
+ * have run: a check is a deterministic function of (model, seed, walks, max_depth, batch size).
+ * Per property the discovery is the hit of the fewest steps, ties to the lowest trace index; an
+ * `eventually` property is hit only at a terminal state of a trace on which it never held.
+ *
+ * Every sr_gpu_bfs_* accessor works on the handle. unique_state_count is SET EQUAL to state_count
+ * (states visited, repeats included: there is no visited set), max_depth is the longest trace in
+ * steps, sr_stats.levels the number of batches, expand_launches the launches and successors =
+ * state_count - traces started; visits are empty and the visit tree is unsupported. Registered
+ * models only (no plugins, no partitions, no symmetry reduction). */
+typedef struct sr_sim_opts {
+    uint32_t struct_size;        /* sizeof this struct in the caller's build                      */
+    int32_t device;              /* HIP device ordinal                                           */
+    uint64_t seed;
+    uint64_t walks;              /* total traces, < 2^40; 0 = run until every property is discovered
+                                    or the target is reached                                     */
+    uint32_t max_depth;          /* steps per trace, 1 .. 2^20; 0 = the default 4096             */
+    int32_t record_walks;        /* keep one record per trace (sr_gpu_sim_walk_records)          */
+    uint64_t target_state_count; /* 0 = none; at least one of walks and target_state_count is required
+                                    (SR_ERR_ARG otherwise: a property may never be discovered)   */
+    int32_t verbose;             /* one log line per batch on stderr                             */
+    int32_t profile;             /* time every launch with HIP events                            */
+} sr_sim_opts;
+/* Zeroes the caller's mirror of `size` bytes (at most the library's own size) and sets struct_size
+ * to what it wrote and max_depth to 4096. */
+void sr_sim_opts_init_sized(sr_sim_opts* opts, uint32_t size);
+/* Spawns the simulation; returns NULL on error (see sr_last_error). Non-blocking. */
+sr_bfs* sr_gpu_sim_spawn(int32_t model_id, const int64_t* params, int32_t nparams, const sr_sim_opts* opts);
+/* record_walks = 1: per trace, by trace index, its steps, end reason (1 terminal, 2 depth, 3 fault)
+ * and the engine's fingerprint of its last state. Returns the number of traces run (at most cap are
+ * written), or SR_ERR_ARG for a handle that is no simulation. */
+int64_t sr_gpu_sim_walk_records(const sr_bfs* sim, uint32_t* steps, uint32_t* end_reason, uint64_t* final_fp, int64_t cap);
+/* The discovery of property `prop`: the trace index and the step of its hit. Returns 1, or 0 if the
+ * property has no discovery (or the handle is no simulation). */
+int32_t sr_gpu_sim_hit(const sr_bfs* sim, int32_t prop, uint64_t* walk, uint32_t* step);
+/* Host-only (no device needed): trace `walk` of a registered model as the device runs it. Writes its
+ * canonical action ids (at most cap), end reason, the fingerprint of its last state and, per
+ * property p < nprops, the step of the trace's hit of p (-1 = none). attempts (may be NULL) receives
+ * the number of drawn slots whose next state was refused. Returns the steps, or a negative SR_ERR_*. */
+int64_t sr_sim_walk(int32_t model_id, const int64_t* params, int32_t nparams, uint64_t seed, uint64_t walk,
+                    uint32_t max_depth, int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp,
+                    int32_t* first_hit_step, int32_t nprops, int32_t* attempts);
 
 /* ---- Partitioned search over several GPUs (no counterpart in the reference,
  * which is single-process shared-memory: src/checker/bfs.rs:70-152) ----

@@ -44,6 +44,24 @@ class sr_opts(ctypes.Structure):
     ]
 
 
+class sr_sim_opts(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("walks", ctypes.c_uint64),
+        ("max_depth", ctypes.c_uint32),
+        ("record_walks", ctypes.c_int32),
+        ("target_state_count", ctypes.c_uint64),
+        ("verbose", ctypes.c_int32),
+        ("profile", ctypes.c_int32),
+    ]
+
+
+# end reasons of a simulated walk (csrc/sim.hpp SimEnd)
+SIM_TERMINAL, SIM_DEPTH, SIM_FAULT = 1, 2, 3
+
+
 class sr_stats(ctypes.Structure):
     _fields_ = [
         ("level_loop_sec", ctypes.c_double),
@@ -148,6 +166,14 @@ SIGNATURES = [
     ("sr_gpu_bfs_visits", ctypes.c_int64, [_P, _I64P, ctypes.c_int64]),
     ("sr_gpu_bfs_visit_tree", ctypes.c_int64, [_P, _I64P, _I64P, ctypes.c_int64]),
     ("sr_gpu_bfs_free", None, [_P]),
+    ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
+    ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
+    ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]),
+    ("sr_gpu_sim_hit", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
+    ("sr_sim_walk", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                     _I64P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("sr_dist_unique_id", ctypes.c_int32, [ctypes.c_char_p]),
     ("sr_dist_init", _P, [ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     ("sr_dist_local_group", ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
@@ -251,6 +277,26 @@ def table_encoding(words, key_bits, slots):
     if st != 0:
         raise ValueError(f"sr_table_encoding: {last_error()} (status {st})")
     return dict(zip(("qbits", "dbits", "bbits", "plimit", "s32", "filter", "filter_log2", "min_cap_log2"), out))
+
+
+def sim_walk(model_id, params, seed, walk, max_depth=4096, nprops=32):
+    """Walk `walk` of the simulation checker on the host (csrc/sim.hpp; no device needed), as the device
+    runs it: dict(steps, end (SIM_TERMINAL / SIM_DEPTH / SIM_FAULT), final_fp, actions (canonical ids),
+    first_hit (per property: the step of the walk's hit, -1 = none), attempts (drawn slots whose next
+    state was refused))."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    acts = (ctypes.c_int64 * max(1, max_depth))()
+    end, att = ctypes.c_int32(), ctypes.c_int32()
+    fp = ctypes.c_uint64()
+    hits = (ctypes.c_int32 * nprops)()
+    n = lib.sr_sim_walk(model_id, arr, len(params), seed, walk, max_depth, acts, max_depth, ctypes.byref(end),
+                        ctypes.byref(fp), hits, nprops, ctypes.byref(att))
+    if n < 0:
+        raise ValueError(f"sr_sim_walk: {last_error()} (status {n})")
+    return {"steps": n, "end": end.value, "final_fp": fp.value, "actions": list(acts[:n]), "first_hit": list(hits),
+            "attempts": att.value}
 
 
 def runtime_versions():

@@ -3,7 +3,7 @@ and the example GpuModel plugin (examples/plugins), which instantiates the same 
 
 The library is several translation units compiled in parallel: engine.hip (the C ABI) and one
 reg_<family>.hip per family of registered models (csrc/registry.hpp), each instantiating the
-engine's kernels for its models. engine.hip is compiled with the source digest (`source_digest`)
+engine's kernels (the BFS engines and the simulation checker, csrc/sim.hpp) for its models. engine.hip is compiled with the source digest (`source_digest`)
 as SR_BUILD_DIGEST, which `sr_build_digest()` returns and `_native.load()` checks."""
 import concurrent.futures
 import hashlib
@@ -18,7 +18,7 @@ UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip"
          "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip",
          "reg_spread.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
-                                                "dist.hpp", "dist_host.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
+                                                "dist.hpp", "dist_host.hpp", "sim.hpp", "kernels_sim.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
                                                 "actor.hpp", "abd_wide.hpp", "table_selftest.hpp"]]
 HEADERS = [os.path.join(ROOT, "include", f) for f in ("stateright_gpu.h", "stateright_gpu_model.hpp")]
 OUT = os.path.join(HERE, "libstateright_gpu.so")

@@ -228,6 +228,44 @@ class CheckerBuilder:
         self._opts.order = N.SR_ORDER_FAST
         return self.spawn_bfs()
 
+    def spawn_simulation(self, seed, walks=None, max_depth=4096, record_walks=False):
+        """The simulation checker (Stateright's `spawn_simulation`, added after the 0.28 mirrored here):
+        `walks` independent random traces of at most `max_depth` steps from the init states, one GPU
+        lane per trace, the properties evaluated on every state. No visited set is kept, so a model
+        too large for `spawn_bfs` still gets discoveries; a run without a discovery proves nothing.
+
+        Trace w is a pure function of (model, seed, w, max_depth) (csrc/sim.hpp), and the check stops
+        after the first whole batch of traces at whose end every property is discovered,
+        `target_state_count` is reached or `walks` traces have run. walks=None needs a
+        `target_state_count` (a property may never be discovered). Honours `device`,
+        `target_state_count`, `verbose` and `profile`; a visitor, partitions / comm,
+        `symmetry_canonical` and plugin models are refused. Non-blocking; call `join()`."""
+        if self._visitor is not None:
+            raise ValueError("spawn_simulation: a visitor has nothing to visit (the walks keep no visit record)")
+        if self._comm is not None or self._partitions > 1:
+            raise ValueError("spawn_simulation: the simulation checker is not partitioned (no partitions / comm)")
+        if self._opts.symmetry:
+            raise ValueError("spawn_simulation: symmetry_canonical has no counterpart (there is no visited set to reduce)")
+        if getattr(self._model, "plugin", None) is not None:
+            raise ValueError("spawn_simulation: plugin models are not simulated (registered models only)")
+        if not 1 <= int(max_depth) <= 2**20:
+            raise ValueError("spawn_simulation: max_depth must be in 1..=2**20")
+        if walks is None and not self._opts.target_state_count:
+            raise ValueError("spawn_simulation: give walks or a target_state_count (a property may never be discovered)")
+        so = N.sr_sim_opts()
+        N.load().sr_sim_opts_init_sized(ctypes.byref(so), ctypes.sizeof(so))
+        so.device = self._opts.device
+        so.seed = int(seed)
+        so.walks = 0 if walks is None else int(walks)
+        so.max_depth = int(max_depth)
+        so.record_walks = int(bool(record_walks))
+        so.target_state_count = self._opts.target_state_count
+        so.verbose = self._opts.verbose
+        so.profile = self._opts.profile
+        if walks is not None and so.walks == 0:
+            raise ValueError("spawn_simulation: walks must be positive")
+        return GpuSimulationChecker(self._model, so)
+
     def serve(self, address=("127.0.0.1", 3000), block=True):
         """`serve` (src/checker.rs:107-113, src/checker/explorer.rs:71-129): spawns the GPU check and
         serves the Explorer's JSON routes (`/.status`, `/.states/<fp>/<fp>/...`) and a small UI over
@@ -267,8 +305,12 @@ class GpuBfsChecker:
                                                        model.MODEL_ID, arr, len(params), ctypes.byref(opts))
         else:
             self._h = lib.sr_gpu_bfs_spawn(model.MODEL_ID, arr, len(params), ctypes.byref(opts))
+        self._spawned("sr_gpu_bfs_spawn")
+
+    def _spawned(self, what):
+        """The state every checker keeps once its spawn call has returned the handle `self._h`."""
         if not self._h:
-            raise CheckerError("sr_gpu_bfs_spawn")
+            raise CheckerError(what)
         self._joined = False
         self._props = None
         self._names = {}
@@ -557,3 +599,63 @@ class GpuBfsChecker:
         extra = f" ({'; '.join(info)})" if info else ""
         raise AssertionError(f'Invalid discovery for "{name}"{extra}, but a valid one was found. '
                              f"found={found.into_actions()}")
+
+
+class GpuSimulationChecker(GpuBfsChecker):
+    """The `Checker` trait over the simulation checker (`CheckerBuilder.spawn_simulation`). `report`,
+    `assert_*`, `discoveries`, `discovery` and `replay` are inherited unchanged, with these meanings:
+    `state_count` is the number of states the walks visited, `unique_state_count` EQUALS it (there is
+    no visited set: repeats count), `max_depth` is the longest walk in steps, and `is_done` means
+    "every property discovered", so `assert_no_discovery` / `assert_properties` of a property that is
+    never violated report that model checking is incomplete: a run without a discovery proves nothing."""
+
+    def __init__(self, model, sim_opts):
+        lib = N.load()
+        self._lib = lib
+        self._model = model
+        self._visitor = None
+        self._comm = None
+        self._sim_opts = sim_opts
+        self._params = list(model.params())
+        arr = (ctypes.c_int64 * max(1, len(self._params)))(*self._params)
+        self._h = lib.sr_gpu_sim_spawn(model.MODEL_ID, arr, len(self._params), ctypes.byref(sim_opts))
+        self._spawned("sr_gpu_sim_spawn")
+
+    def walk_records(self):
+        """record_walks=True: [(steps, end reason, fingerprint of the last state)] per walk, by walk
+        index (end reason: 1 terminal, 2 depth, 3 fault)."""
+        n = self._lib.sr_gpu_sim_walk_records(self._h, None, None, None, 0)
+        if n < 0:
+            raise CheckerError("sr_gpu_sim_walk_records", n)
+        steps = (ctypes.c_uint32 * max(1, n))()
+        end = (ctypes.c_uint32 * max(1, n))()
+        fp = (ctypes.c_uint64 * max(1, n))()
+        self._lib.sr_gpu_sim_walk_records(self._h, steps, end, fp, n)
+        return list(zip(steps[:n], end[:n], fp[:n]))
+
+    def walk_records_arrays(self):
+        """walk_records as three numpy arrays (steps, end reason, fingerprint)."""
+        import numpy as np
+        n = self._lib.sr_gpu_sim_walk_records(self._h, None, None, None, 0)
+        if n < 0:
+            raise CheckerError("sr_gpu_sim_walk_records", n)
+        steps = np.zeros(max(1, n), dtype=np.uint32)
+        end = np.zeros(max(1, n), dtype=np.uint32)
+        fp = np.zeros(max(1, n), dtype=np.uint64)
+        self._lib.sr_gpu_sim_walk_records(self._h, steps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          end.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          fp.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n)
+        return steps[:n], end[:n], fp[:n]
+
+    def hit(self, name):
+        """The discovery of property `name` as (step, walk index): the hit of the fewest steps, ties
+        to the lowest walk index; None without a discovery."""
+        walk, step = ctypes.c_uint64(), ctypes.c_uint32()
+        if not self._lib.sr_gpu_sim_hit(self._h, self._prop_index(name), ctypes.byref(walk), ctypes.byref(step)):
+            return None
+        return step.value, walk.value
+
+    def host_walk(self, i):
+        """Walk `i` of this check re-walked on the host (`_native.sim_walk`)."""
+        return N.sim_walk(self._model.MODEL_ID, self._params, self._sim_opts.seed, i, self._sim_opts.max_depth,
+                          max(1, len(self.properties())))

@@ -365,6 +365,7 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             need(3);
             return f(LinearEquation{(u32)(p[0] & 0xff), (u32)(p[1] & 0xff), (u32)(p[2] & 0xff)});
         case SR_MODEL_BINARY_CLOCK: return f(BinaryClock{});
+        case SR_MODEL_DGRAPH: return f(DGraph::make(p, np, -1));  // (host tables only)
         case SR_MODEL_2PC:
             need(1);
             if (p[0] < 1 || p[0] > 14) throw Error(SR_ERR_UNSUPPORTED, "2pc: rm_count must be in 1..=14");
@@ -502,6 +503,72 @@ int64_t sr_selftest_describe(int32_t model, const int64_t* p, int32_t np, int64_
     } catch (const Error& x) {
         set_error(x.what());
         return x.code;
+    }
+}
+
+void sr_sim_opts_init_sized(sr_sim_opts* o, uint32_t size) {
+    const uint32_t n = size < (uint32_t)sizeof(sr_sim_opts) ? size : (uint32_t)sizeof(sr_sim_opts);
+    if (!o || n < sizeof(uint32_t)) return;
+    sr_sim_opts d;
+    std::memset(&d, 0, sizeof(d));
+    d.struct_size = n;
+    d.max_depth = 4096;
+    std::memcpy(o, &d, n);  // only the caller's own bytes
+}
+
+sr_bfs* sr_gpu_sim_spawn(int32_t model_id, const int64_t* params, int32_t nparams, const sr_sim_opts* opts) {
+    try {
+        const sr_sim_opts so = normalized_sim_opts(opts);
+        if (sr_device_count() <= 0) throw Error(SR_ERR_NO_DEVICE, "no HIP device visible");
+        sr_opts o = normalized_opts(nullptr);
+        o.device = so.device;
+        EngineArgs a{model_id, params, nparams, &o, false, nullptr, 0};
+        a.sim = &so;
+        return start(make_model_engine(a));
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return nullptr;
+    }
+}
+
+int64_t sr_gpu_sim_walk_records(const sr_bfs* b, uint32_t* steps, uint32_t* end_reason, uint64_t* final_fp, int64_t cap) {
+    const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
+    if (!e) {
+        set_error("not a simulation handle");
+        return SR_ERR_ARG;
+    }
+    return e->sim_records(steps, end_reason, final_fp, std::max<int64_t>(cap, 0));
+}
+
+int32_t sr_gpu_sim_hit(const sr_bfs* b, int32_t prop, uint64_t* walk, uint32_t* step) {
+    const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
+    return e && e->sim_hit(prop, walk, step) ? 1 : 0;
+}
+
+int64_t sr_sim_walk(int32_t model, const int64_t* p, int32_t np, uint64_t seed, uint64_t walk, uint32_t max_depth,
+                    int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp, int32_t* first_hit_step,
+                    int32_t nprops, int32_t* attempts) {
+    try {
+        if (!max_depth || max_depth > SIM_MAX_DEPTH) throw Error(SR_ERR_ARG, "simulation: max_depth must be in 1..=2^20");
+        if (walk >= SIM_MAX_WALKS) throw Error(SR_ERR_ARG, "simulation: walk must be below 2^40");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            const SimHostWalk h = sim_host_walk(m, seed, walk, max_depth);
+            for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
+            if (end_reason) *end_reason = (int32_t)h.end;
+            if (final_fp) *final_fp = h.final_fp;
+            for (int32_t q = 0; first_hit_step && q < nprops; ++q) first_hit_step[q] = q < M::NPROPS ? h.first_hit[q] : -1;
+            if (attempts) *attempts = (int32_t)h.redraws;
+            return (i64)h.steps;
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_sim_walk: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
     }
 }
 

@@ -1,17 +1,19 @@
 // The compiled-in GpuModel registry, split into families that compile as separate translation units
 // (reg_*.hip, built in parallel by stateright_amd/build.py and linked into libstateright_gpu.so).
-// Each family instantiates the single-GPU Engine<M> and the partitioned DistEngine<M> for its
-// models; engine.hip maps a model id (SR_MODEL_*) to its family.
+// Each family instantiates the single-GPU Engine<M>, the partitioned DistEngine<M> and the simulation
+// checker SimEngine<M> (sim.hpp) for its models; engine.hip maps a model id (SR_MODEL_*) to its family.
 #pragma once
 #include <memory>
 
 #include "engine.hpp"
 #include "dist.hpp"
+#include "sim.hpp"
 
 namespace sr {
 
 // What a spawn asks for: the model's integer parameters and options, and for the partitioned
-// search its communicator (or none) and virtual partitions.
+// search its communicator (or none) and virtual partitions; for a simulation (sim != nullptr) the
+// walk options, with `o` carrying the device only.
 struct EngineArgs {
     int model;
     const i64* p;
@@ -20,15 +22,20 @@ struct EngineArgs {
     bool dist;
     Comm* comm;
     int vparts;
+    const sr_sim_opts* sim = nullptr;
     void need(int k) const {
         if (np < k) throw Error(SR_ERR_ARG, "model " + std::to_string(model) + " needs " + std::to_string(k) + " params");
     }
 };
 
-// Engine<M> or DistEngine<M>. EV: a model with `eventually` properties runs partitioned as
+// Engine<M>, DistEngine<M> or SimEngine<M> (plain models only: no Canon<M>, no EvBits<M>). EV: a model with `eventually` properties runs partitioned as
 // EvBits<M> (models.hpp).
 template <class M, bool EV = false>
 std::unique_ptr<EngineBase> make_for(const M& m, const EngineArgs& a) {
+    if (a.sim) {
+        if constexpr (is_canon<M>::value || is_evbits<M>::value) throw Error(SR_ERR_UNSUPPORTED, "simulation: symmetry reduction has no counterpart");
+        else return std::make_unique<SimEngine<M>>(m, *a.sim);
+    }
     if (!a.dist) return std::make_unique<Engine<M>>(m, *a.o);
     if constexpr (EV && has_emask<M>::value) {
         if (model_emask(m)) return std::make_unique<DistEngine<EvBits<M>>>(EvBits<M>(m), *a.o, a.comm, a.vparts);

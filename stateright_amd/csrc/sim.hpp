@@ -1,0 +1,446 @@
+// Random-walk simulation checker: the counterpart of the simulation checker Stateright gained after
+// the 0.28 this engine mirrors. Many independent random traces ("walks") run from the init states,
+// the properties are evaluated on every state of a walk, and NO visited set is kept: a check whose
+// reachable set fits no card still gets discoveries. A run without a discovery proves nothing.
+//
+// The walk is defined ONCE here, as SR_HD templates over a GpuModel M (models.hpp): the kernel
+// (kernels_sim.hpp simulate_walks) and the host re-walk (sim_host_walk: discovery paths, the
+// host-only sr_sim_walk entry point) instantiate the same code, so a walk is a pure function of
+// (model, seed, walk index w, max_depth), on either side.
+//
+// Randomness (part of the definition). A counter-based generator, no per-lane state:
+//   sim_walk_key(seed, w) = fmix64(seed + 0x9E3779B97F4A7C15 * (w + 1))
+//   r(seed, w, t, k)      = fmix64((sim_walk_key(seed, w) ^ (t << 32 | k)) + 0x632BE59BD9B4E019)
+// t is the step (0 .. max_depth <= 2^20), k the attempt of that step; the init state is drawn with
+// t = 0, k = SIM_K_INIT (no attempt count reaches it: max_actions is an int). fmix64 is a bijection,
+// so for one walk distinct (t, k) give distinct draws' inputs. To choose one of n:
+//   sim_choose(r, n) = ((r >> 32) * n) >> 32          (n < 2^32; no modulo)
+//
+// The walk of index w:
+//   s_0 = init state number sim_choose(r(seed, w, 0, SIM_K_INIT), init_count) of init_states_of(m).
+//   Visiting s_t: one state is counted; then for every property p, in order:
+//     always / sometimes with discovers(p, s_t): a hit (p, t, w) (the first of the walk per property);
+//     eventually with discovers(p, s_t): bit p of the walk's `sat` mask is set.
+//   If the model has `faulted` and it holds at s_t, the walk ends with SIM_FAULT.
+//   If t == max_depth the walk ends with SIM_DEPTH (a non-terminal end records nothing for
+//   `eventually`: `assert_discovery` demands a terminal last state, src/checker.rs:306-323).
+//   Stepping: mask = enabled(s_t), attempt k = 0. While mask is non-empty: a = its
+//   sim_choose(r(seed, w, t, k), popcount(mask))-th set bit (ascending slot order); if
+//   apply(s_t, a, out) then s_{t+1} = out; else bit a is cleared and k += 1 (`next_state` is None
+//   or outside the boundary, src/checker/bfs.rs:231-234). If the mask runs empty, s_t is terminal:
+//   every `eventually` property not in `sat` is a hit (p, t, w) and the walk ends with SIM_TERMINAL
+//   (bfs.rs:265-272).
+// The walk uses the model's plain `enabled` and `apply` (2pc's self-loop actions are steps like any
+// other); `enabled_moves` and `self_loops` would change which slots are candidates. Canon<M> and
+// EvBits<M> are not simulated. Every loop is bounded: steps by max_depth (<= 2^20), redraws by the
+// number of enabled slots (<= max_actions).
+//
+// A check (SimEngine) runs the walks 0 .. walks-1 in batches of consecutive indices, one launch per
+// batch, and stops after the first WHOLE batch at whose end every property has a hit, state_count
+// reached target_state_count, or the walks are exhausted; so a check is a deterministic function of
+// (model, seed, walks, max_depth, batch size). Per property the hit with the smallest (t, w) is
+// kept: the shortest trace, ties to the lowest walk index. There is no visited set, so
+// `unique` is SET EQUAL to state_count (every visited state counts, repeats included), `max_depth`
+// is the longest walk in steps, and `is_done` means "every property discovered".
+#pragma once
+#include "engine.hpp"
+
+namespace sr {
+
+enum SimEnd : u32 { SIM_RUNNING = 0, SIM_TERMINAL = 1, SIM_DEPTH = 2, SIM_FAULT = 3 };
+constexpr u32 SIM_K_INIT = 0xFFFFFFFFu;
+constexpr u32 SIM_MAX_DEPTH = 1u << 20;
+constexpr u64 SIM_MAX_WALKS = 1ull << 40;
+constexpr u64 SIM_NO_HIT = ~0ull;
+
+SR_HD u64 sim_walk_key(u64 seed, u64 w) { return fmix64(seed + 0x9E3779B97F4A7C15ull * (w + 1)); }
+SR_HD u64 sim_rand_keyed(u64 key, u32 t, u32 k) { return fmix64((key ^ ((u64)t << 32 | k)) + 0x632BE59BD9B4E019ull); }
+SR_HD u64 sim_rand(u64 seed, u64 w, u32 t, u32 k) { return sim_rand_keyed(sim_walk_key(seed, w), t, k); }
+SR_HD u32 sim_choose(u64 r, u32 n) { return (u32)(((r >> 32) * (u64)n) >> 32); }
+// Key of a hit: the minimum over hits is the shortest trace, then the lowest walk index.
+SR_HD u64 sim_hit_key(u32 t, u64 w) { return (u64)t << 40 | w; }
+
+// A walk in progress: what a lane of the kernel keeps in registers.
+template <class M>
+struct SimWalk {
+    u64 s[M::W];
+    u64 key;        // sim_walk_key(seed, w)
+    u32 t;          // steps taken so far: s is s_t
+    u32 sat;        // `eventually` properties whose condition held on the way
+    u32 hit;        // always / sometimes properties this walk already reported
+    u32 redraws;    // slots drawn whose apply() refused (all steps)
+};
+
+template <class M>
+SR_HD void sim_start(SimWalk<M>& wk, u64 seed, u64 w, const u64* inits, u32 init_count) {
+    wk.key = sim_walk_key(seed, w);
+    const u32 i = sim_choose(sim_rand_keyed(wk.key, 0, SIM_K_INIT), init_count);
+#pragma unroll
+    for (int j = 0; j < M::W; ++j) wk.s[j] = inits[(size_t)i * M::W + j];
+    wk.t = 0;
+    wk.sat = 0;
+    wk.hit = 0;
+    wk.redraws = 0;
+}
+
+// The j-th (0-based, ascending) set bit of a mask of MW words holding more than j set bits.
+template <int MW>
+SR_HD int sim_select(const u64* mask, u32 j) {
+    int a = 0;
+#pragma unroll
+    for (int w = 0; w < MW; ++w) {
+        const u32 c = (u32)__builtin_popcountll(mask[w]);
+        if (j < c) {
+            u64 bits = mask[w];
+            for (u32 i = 0; i < j; ++i) bits &= bits - 1;  // (j < 64)
+            a = w * 64 + __builtin_ctzll(bits);
+            break;
+        }
+        j -= c;
+    }
+    return a;
+}
+
+// Visits s_t and takes one step. emask: the model's `eventually` properties (the others are reported
+// where discovers() holds). on_hit(p, t) is called for every hit of the walk; on_step(s_t, a)
+// before the walk moves on through slot a.
+// Returns SIM_RUNNING (wk now holds s_{t+1}) or the reason the walk ended at s_t.
+template <class M, class Hit, class Step>
+SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step) {
+#pragma unroll
+    for (int p = 0; p < M::NPROPS; ++p) {
+        if (emask >> p & 1) {
+            if (!(wk.sat >> p & 1) && m.discovers(p, wk.s)) wk.sat |= 1u << p;
+        } else if (!(wk.hit >> p & 1) && m.discovers(p, wk.s)) {
+            wk.hit |= 1u << p;
+            on_hit(p, wk.t);
+        }
+    }
+    if constexpr (has_faulted<M>::value) {
+        if (m.faulted(wk.s)) return SIM_FAULT;
+    }
+    if (wk.t >= max_depth) return SIM_DEPTH;
+    u64 mask[M::MW];
+    m.enabled(wk.s, mask);
+    u32 left = 0;
+#pragma unroll
+    for (int w = 0; w < M::MW; ++w) left += (u32)__builtin_popcountll(mask[w]);
+    for (u32 k = 0; left; ++k, --left) {  // (at most the enabled slots: each round clears one)
+        const int a = sim_select<M::MW>(mask, sim_choose(sim_rand_keyed(wk.key, wk.t, k), left));
+        u64 out[M::W];
+        if (m.apply(wk.s, a, out)) {
+            on_step(wk.s, a);
+#pragma unroll
+            for (int j = 0; j < M::W; ++j) wk.s[j] = out[j];
+            wk.t += 1;
+            return SIM_RUNNING;
+        }
+#pragma unroll
+        for (int w = 0; w < M::MW; ++w)  // (no dynamic index: the mask stays in registers)
+            if (w == (a >> 6)) mask[w] &= ~(1ull << (a & 63));
+        wk.redraws += 1;
+    }
+    for (u32 e = emask & ~wk.sat; e; e &= e - 1) on_hit(__builtin_ctz(e), wk.t);
+    return SIM_TERMINAL;
+}
+
+}  // namespace sr
+
+#include "kernels_sim.hpp"
+
+namespace sr {
+
+// One walk on the host, as the device runs it.
+struct SimHostWalk {
+    u32 steps = 0, end = SIM_RUNNING, redraws = 0;
+    u64 final_fp = 0;
+    std::vector<i64> actions;   // canonical action ids, one per step
+    std::vector<i64> states;    // (steps + 1) descriptions (only when asked for)
+    std::vector<u64> fps;       // (steps + 1) fingerprints (only when asked for)
+    std::vector<int> first_hit; // per property: the step of its hit, -1 = none
+};
+
+// The whole walk w. describe: also the descriptions and fingerprints of its first keep + 1 states and
+// the action ids of its first keep steps (a discovery path is the walk cut at its hit's step).
+template <class M>
+SimHostWalk sim_host_walk(const M& m, u64 seed, u64 w, u32 max_depth, bool describe = false, u32 keep = ~0u) {
+    const std::vector<u64> inits = init_states_of(m);
+    const u32 k = (u32)(inits.size() / M::W);
+    if (!k) throw Error(SR_ERR_ARG, "simulation: the model has no init state");
+    SimHostWalk r;
+    r.first_hit.assign(M::NPROPS, -1);
+    SimWalk<M> wk;
+    sim_start<M>(wk, seed, w, inits.data(), k);
+    const u32 emask = model_emask(m);
+    const int wd = m.describe_width();
+    auto emit = [&](const u64* s, u32 t) {
+        if (!describe || t > keep) return;
+        const size_t o = r.states.size();
+        r.states.resize(o + wd);
+        m.describe(s, &r.states[o]);
+        r.fps.push_back(state_fp<M>(s));
+    };
+    for (;;) {
+        const u32 t = wk.t;
+        r.end = sim_advance(m, wk, max_depth, emask, [&](int p, u32 th) { if (r.first_hit[p] < 0) r.first_hit[p] = (int)th; },
+                            [&](const u64* s, int a) {
+                                emit(s, t);
+                                if (t < keep) r.actions.push_back(m.action_id(s, a));
+                            });
+        if (r.end != SIM_RUNNING) break;
+    }
+    emit(wk.s, wk.t);
+    r.steps = wk.t;
+    r.redraws = wk.redraws;
+    r.final_fp = state_fp<M>(wk.s);
+    return r;
+}
+
+// What the C ABI's simulation accessors ask of a handle (a BFS handle is none).
+class SimEngineBase : public EngineBase {
+  public:
+    virtual bool sim_hit(int p, u64* walk, u32* step) const = 0;
+    virtual i64 sim_records(u32* steps, u32* end, u64* fp, i64 cap) const = 0;
+};
+
+// SR_SIM_REFILL: 1 = the persistent form (a lane whose walk ended takes the next unstarted index of
+// the batch), 0 = one walk per lane. Both give the same per-walk records and hits. The default is
+// the static form: profiles/sim_walk_rate.txt.
+inline bool sim_refill_default() {
+    if (const char* e = std::getenv("SR_SIM_REFILL")) return std::atoi(e) != 0;
+    return false;
+}
+
+// Steps a launch may take at most (walks of a batch x max_depth): at the ~1.5e10 steps/s of the slowest
+// model measured (paxos C=3, profiles/sim_walk_rate.txt) a launch whose walks all run to max_depth
+// takes ~9 ms, and a model several times slower stays in the tens of milliseconds. A batch is a whole
+// launch followed by a read-back of the counters, so deep walks mean small batches: at the default
+// max_depth of 4096 a batch is 32 768 walks, half a wave per SIMD of a 256-CU part, and a check
+// whose walks really run that deep is launch-bound at a fraction of the profile's rates (taken at
+// max_depth 256, 524 288 walks per batch); walks that end early only make the launch shorter.
+// SR_SIM_BATCH (tests) sets the walks per batch directly.
+constexpr u64 SIM_STEP_BUDGET = 1ull << 27;
+constexpr u64 SIM_BATCH_MAX = 1ull << 24;
+
+template <class M>
+class SimEngine final : public SimEngineBase {
+    static constexpr int W = M::W;
+    static_assert(!is_canon<M>::value && !is_evbits<M>::value, "Canon<M> and EvBits<M> are not simulated");
+    static_assert(M::NPROPS <= MAX_PROPS, "too many properties");
+
+  public:
+    SimEngine(M m, const sr_sim_opts& o) : m_(m), o_(o), emask_(model_emask(m)), refill_(sim_refill_default()) {
+        disc.resize(M::NPROPS);
+        hits_.assign(M::NPROPS, SIM_NO_HIT);
+        inits_ = init_states_of(m_);
+        if (inits_.empty()) throw Error(SR_ERR_ARG, "simulation: the model has no init state");
+        batch_ = std::max<u64>(1, std::min<u64>(SIM_BATCH_MAX, SIM_STEP_BUDGET / o_.max_depth));
+        if (const char* e = std::getenv("SR_SIM_BATCH"))
+            if (std::atoll(e) > 0) batch_ = std::min<u64>((u64)std::atoll(e), SIM_BATCH_MAX);
+        if (const char* e = std::getenv("SR_SIM_GRID"))
+            if (std::atoi(e) > 0) grid_cap_ = (u32)std::atoi(e);
+    }
+
+    int nprops() const override { return M::NPROPS; }
+    const char* prop_name(int p) const override { return m_.prop_name(p); }
+    int expectation(int p) const override { return m_.expectation(p); }
+    int width() const override { return m_.describe_width(); }
+    std::string action_name(i64 id) const override { return m_.action_name(id); }
+    i64 action_id_bound() const override { return m_.action_id_bound(); }
+    int init_count() const override { return (int)(inits_.size() / W); }
+    int replay(int init, const i64* ids, int n, std::vector<i64>& states, std::vector<int>& conds, std::vector<int>* all_conds,
+               int* terminal) const override {
+        return replay_model(m_, init, ids, n, states, conds, all_conds, terminal);
+    }
+    int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
+                std::vector<i64>& states) const override {
+        return explore_model(m_, fps, n, action, has, fp, states);
+    }
+    std::vector<i64> visits() const override { return {}; }
+
+    void run() override {
+        const auto t_start = Clock::now();
+        SR_HIP(hipSetDevice(o_.device));
+        CtxLease lease(o_.device);
+        hipStream_t stream = lease.c->stream;
+        stats = sr_stats{};
+        stats.words_per_state = W;
+        const u32 k = (u32)(inits_.size() / W);
+        SimArgs a{};
+        a.seed = o_.seed;
+        a.max_depth = o_.max_depth;
+        a.init_count = k;
+        a.emask = emask_;
+        InlineStates inl{};
+        DBuf<u64> init_d;
+        if ((u64)k * W <= ROOTS_INLINE_WORDS) {
+            std::copy(inits_.begin(), inits_.end(), inl.w);
+        } else {
+            init_d.alloc(o_.device, inits_.size());
+            SR_HIP(hipMemcpyAsync(init_d.p, inits_.data(), inits_.size() * sizeof(u64), hipMemcpyHostToDevice, stream));
+            a.inits = init_d.p;
+        }
+        DBuf<u64> dev;  // SimDevice: the counter shards, the best hits, the batch cursor
+        dev.alloc(o_.device, (sizeof(SimDevice) + 7) / 8);
+        SimDevice* sd = reinterpret_cast<SimDevice*>(dev.p);
+        SR_HIP(hipMemsetAsync(sd, 0, sizeof(SimDevice), stream));
+        SR_HIP(hipMemsetAsync(sd->best, 0xff, sizeof(sd->best), stream));
+        a.dev = sd;
+        DBuf<SimRecord> rec;
+        const u64 total = o_.walks;  // 0: until every property is discovered or the target is reached
+        if (o_.record_walks) rec.alloc(o_.device, (size_t)std::min<u64>(batch_, total ? total : batch_));
+        records_.clear();
+        int ndev = 0;
+        SR_HIP(hipDeviceGetAttribute(&ndev, hipDeviceAttributeMultiprocessorCount, o_.device));
+        if (ndev <= 0) ndev = 256;
+
+        u64 states = 0, started = 0, ended[4] = {0, 0, 0, 0};
+        u32 longest = 0;
+        const auto t_loop = Clock::now();
+        std::vector<SimDevice> host(1);
+        for (u64 b0 = 0;;) {
+            const u64 left = total ? total - b0 : SIM_MAX_WALKS - b0;
+            const u32 n = (u32)std::min<u64>(batch_, left);
+            if (!n) break;
+            a.b0 = b0;
+            a.n = n;
+            a.records = o_.record_walks ? rec.p : nullptr;
+            // the persistent form: at most SIM_PERSIST_WAVES waves per compute unit walk the whole batch
+            // (a batch beyond that many lanes is what the refill hands out; SR_SIM_GRID, for tests and
+            // measurements, sets the cap in workgroups)
+            u32 grid = blocks_for(n, SIM_BLOCK);
+            if (refill_) grid = std::min<u32>(grid, grid_cap_ ? grid_cap_ : (u32)ndev * SIM_PERSIST_WAVES / (SIM_BLOCK / 64));
+            const size_t ev = 2 * stats.expand_launches;
+            if (o_.profile) SR_HIP(hipEventRecord(lease.c->event(ev), stream));
+            if (refill_) simulate_walks<M, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else simulate_walks<M, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            SR_HIP(hipGetLastError());
+            if (o_.profile) SR_HIP(hipEventRecord(lease.c->event(ev + 1), stream));
+            stats.expand_launches++;
+            launch_frontier.push_back(n);
+            launch_probes.push_back(0);
+            launch_cas.push_back(0);
+            SR_HIP(hipMemcpyAsync(host.data(), sd, sizeof(SimDevice), hipMemcpyDeviceToHost, stream));
+            if (o_.record_walks) {
+                const size_t o = records_.size();
+                records_.resize(o + n);
+                SR_HIP(hipMemcpyAsync(&records_[o], rec.p, (size_t)n * sizeof(SimRecord), hipMemcpyDeviceToHost, stream));
+            }
+            // the next batch starts from zeroed shards and cursor (the best hits carry over)
+            SR_HIP(hipMemsetAsync(sd, 0, offsetof(SimDevice, best), stream));
+            SR_HIP(stream_sync(stream));
+            for (u32 i = 0; i < NSHARD; ++i) {
+                const SimShard& s = host[0].shard[i];
+                states += s.states;
+                for (int r = 1; r < 4; ++r) ended[r] += s.ended[r];
+                longest = std::max(longest, s.longest);
+            }
+            started += n;
+            b0 += n;
+            stats.levels++;
+            bool all = true;
+            for (int p = 0; p < M::NPROPS; ++p) {
+                hits_[p] = host[0].best[p];
+                disc[p].found = hits_[p] != SIM_NO_HIT;
+                all = all && disc[p].found;
+            }
+            state_count = states;
+            unique = states;  // no visited set: every visited state counts
+            max_depth = longest;
+            if (o_.verbose)
+                std::fprintf(stderr, "[sr] simulation batch %llu: walks %llu, states %llu, longest %u\n",
+                             (unsigned long long)stats.levels, (unsigned long long)started, (unsigned long long)states, longest);
+            if (ended[SIM_FAULT]) throw Error(SR_ERR_UNSUPPORTED, model_fault_text(m_));
+            if (ended[1] + ended[2] + ended[3] != started)
+                throw Error(SR_ERR_HIP, "simulation: a batch ended " + std::to_string(ended[1] + ended[2] + ended[3]) + " of " +
+                                            std::to_string(started) + " walks");
+            if (all) {
+                reference_done = true;
+                break;
+            }
+            if (o_.target_state_count && states >= o_.target_state_count) break;
+            if (b0 >= SIM_MAX_WALKS) break;
+        }
+        stats.successors = states - started;
+        stats.level_loop_sec = secs(t_loop, Clock::now());
+        if (o_.profile && stats.expand_launches) {
+            double ms = 0;
+            launch_ms.assign(stats.expand_launches, 0.0);
+            for (u64 i = 0; i < stats.expand_launches; ++i) {
+                float t = 0;
+                SR_HIP(hipEventElapsedTime(&t, lease.c->event(2 * i), lease.c->event(2 * i + 1)));
+                ms += t;
+                launch_ms[i] = t;
+            }
+            stats.expand_kernel_ms = ms;
+        }
+        stats.total_sec = secs(t_start, Clock::now());
+    }
+
+    // The discovery of property p: walk w of its hit (t, w), cut at step t, re-walked on the host.
+    SimHostWalk discovery_walk(int p) const {
+        const u64 key = hits_[p];
+        const u32 t = (u32)(key >> 40);
+        const u64 w = key & (SIM_MAX_WALKS - 1);
+        SimHostWalk r = sim_host_walk(m_, o_.seed, w, o_.max_depth, true, t);
+        if (r.steps < t || r.first_hit[p] != (int)t)
+            throw Error(SR_ERR_NONDETERMINISM, "simulation: the host walk " + std::to_string(w) + " does not reproduce the device's hit of \"" +
+                                                   std::string(m_.prop_name(p)) + "\" at step " + std::to_string(t));
+        return r;
+    }
+    int chain(int p, std::vector<u64>& out) override {
+        out.clear();
+        if (p < 0 || p >= M::NPROPS || hits_[p] == SIM_NO_HIT) return 0;
+        out = discovery_walk(p).fps;
+        return (int)out.size();
+    }
+    int path(int p, std::vector<i64>& actions, std::vector<i64>& states) override {
+        if (p < 0 || p >= M::NPROPS || hits_[p] == SIM_NO_HIT) return -1;
+        SimHostWalk r = discovery_walk(p);
+        actions = std::move(r.actions);
+        states = std::move(r.states);
+        return (int)actions.size();
+    }
+
+    bool sim_hit(int p, u64* walk, u32* step) const override {
+        if (p < 0 || p >= M::NPROPS || hits_[p] == SIM_NO_HIT) return false;
+        if (walk) *walk = hits_[p] & (SIM_MAX_WALKS - 1);
+        if (step) *step = (u32)(hits_[p] >> 40);
+        return true;
+    }
+    i64 sim_records(u32* steps, u32* end, u64* fp, i64 cap) const override {
+        for (i64 i = 0; i < std::min<i64>(cap, (i64)records_.size()); ++i) {
+            if (steps) steps[i] = records_[i].steps;
+            if (end) end[i] = records_[i].end;
+            if (fp) fp[i] = records_[i].fp;
+        }
+        return (i64)records_.size();
+    }
+
+  private:
+    M m_;
+    sr_sim_opts o_;
+    u32 emask_;
+    bool refill_;
+    u32 grid_cap_ = 0;  // SR_SIM_GRID: the persistent form's grid cap in workgroups (0: by compute units)
+    u64 batch_ = 1;
+    std::vector<u64> inits_;
+    std::vector<u64> hits_;          // per property: sim_hit_key of the best hit, SIM_NO_HIT = none
+    std::vector<SimRecord> records_; // record_walks: one per walk started, by walk index
+};
+
+// Validated copy of a caller's sr_sim_opts (a shorter mirror is zero-extended, then defaulted).
+inline sr_sim_opts normalized_sim_opts(const sr_sim_opts* opts) {
+    sr_sim_opts o;
+    std::memset(&o, 0, sizeof(o));
+    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
+    o.struct_size = sizeof(sr_sim_opts);
+    if (!o.max_depth) o.max_depth = 4096;
+    if (o.max_depth > SIM_MAX_DEPTH) throw Error(SR_ERR_ARG, "simulation: max_depth must be in 1..=2^20");
+    if (o.walks >= SIM_MAX_WALKS) throw Error(SR_ERR_ARG, "simulation: walks must be below 2^40");
+    if (!o.walks && !o.target_state_count)
+        throw Error(SR_ERR_ARG, "simulation: walks or target_state_count must be set (a property may never be discovered)");
+    return o;
+}
+
+}  // namespace sr
