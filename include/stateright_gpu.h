@@ -76,7 +76,10 @@ enum sr_model_id {
                                      free_bits<=24; loops<=4; mark < 2^free_bits) test fixture: the subsets of
                                      free_bits bits packed into a pseudo-random key of key_bits bits, so the
                                      visited set's slot encoding is a parameter; 2^free_bits states, `loops`
-                                     unreported self-loops per state (stateright_amd/csrc/models.hpp Spread) */
+                                     unreported self-loops per state (stateright_amd/csrc/models.hpp Spread).
+                                     Optionally followed by (roots, dup): the init states are the subsets
+                                     0 .. roots-1, then 0 .. dup-1 again; 1 <= roots <= 2^free_bits,
+                                     dup <= roots, roots + dup <= 512 (default 1, 0) */
 };
 
 /* Visit order inside a BFS level. */
@@ -163,7 +166,20 @@ typedef struct sr_stats {
                                     bit 8 4-byte slots, bits 16-23 log2 of the filter's entries (0: no
                                     filter), bit 24 compact (4-byte) filter entries (this field was
                                     reserved0 and always 0 before)                                 */
+    uint32_t root_path;          /* how the init states entered the check (enum sr_root_path)      */
+    uint32_t reserved1;
 } sr_stats;
+
+/* sr_stats.root_path: the code path that put the init states into the visited set and level 0. */
+enum sr_root_path {
+    SR_ROOTS_INLINE = 1,   /* one launch, the states in the kernel arguments (at most 32 words of them);
+                              simulation: the walks read them from the kernel arguments            */
+    SR_ROOTS_FUSED = 2,    /* a host copy, then one workgroup (more than 32 words, at most 256 states) */
+    SR_ROOTS_LAUNCHES = 3, /* a host copy, then insert, evaluate and publish launches (more than 256) */
+    SR_ROOTS_HEAD = 4,     /* partitioned search: into the replicated head                         */
+    SR_ROOTS_PARTS = 5,    /* partitioned search: each partition takes the states it owns          */
+    SR_ROOTS_BUFFER = 6    /* simulation: the walks read them from device memory (more than 32 words) */
+};
 
 typedef struct sr_bfs sr_bfs;
 

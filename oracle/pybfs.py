@@ -98,12 +98,19 @@ def spread_describe(words, key_bits, free_bits, x):
     return tuple(d)
 
 
-def spread_bfs(words, key_bits, free_bits, loops=0, mark=0):
-    """Spread(words, key_bits, free_bits, loops, mark) on bfs(): states are described states
-    (spread_describe); action j < free_bits sets bit j of x where it is clear, actions free_bits ..
-    free_bits + loops - 1 return the state itself. always "in range" (x < 2^free_bits), sometimes
-    "marked" (x == mark). Adds `actions`: per discovery, the action ids along its path."""
+def spread_inits(roots=1, dup=0):
+    """The subsets that are Spread's init states, in init order: 0 .. roots-1, then 0 .. dup-1 again."""
+    return list(range(roots)) + list(range(dup))
+
+
+def spread_bfs(words, key_bits, free_bits, loops=0, mark=0, roots=1, dup=0):
+    """Spread(words, key_bits, free_bits, loops, mark, roots, dup) on bfs(): states are described
+    states (spread_describe); action j < free_bits sets bit j of x where it is clear, actions
+    free_bits .. free_bits + loops - 1 return the state itself. always "in range" (x < 2^free_bits),
+    sometimes "marked" (x == mark). The init states are spread_inits(roots, dup). Adds `actions`: per
+    discovery, the action ids along its path (each step sets one bit, whichever root the path starts at)."""
     assert words in (1, 2, 4) and free_bits < key_bits <= min(64 * words, 128) and 0 <= loops <= 4
+    assert 1 <= roots <= 1 << free_bits and 0 <= dup <= roots and roots + dup <= 512
     packed = {}
 
     def d(x):  # (two subsets never pack alike: x is the key's low bits)
@@ -117,7 +124,7 @@ def spread_bfs(words, key_bits, free_bits, loops=0, mark=0):
     def next_state(s, a):
         return d(s[0] | 1 << a) if a < free_bits else s
 
-    r = bfs([d(0)], actions, next_state,
+    r = bfs([d(x) for x in spread_inits(roots, dup)], actions, next_state,
             [("in range", ALWAYS, lambda s: s[0] < 1 << free_bits), ("marked", SOMETIMES, lambda s: s[0] == mark)])
     r["actions"] = {name: [(b[0] ^ a[0]).bit_length() - 1 for a, b in zip(path, path[1:])]
                     for name, path in r["discoveries"].items()}

@@ -26,6 +26,8 @@ SR_MODEL_SPREAD = 14
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
+# sr_stats.root_path (enum sr_root_path)
+SR_ROOTS_INLINE, SR_ROOTS_FUSED, SR_ROOTS_LAUNCHES, SR_ROOTS_HEAD, SR_ROOTS_PARTS, SR_ROOTS_BUFFER = 1, 2, 3, 4, 5, 6
 
 
 class sr_opts(ctypes.Structure):
@@ -88,6 +90,8 @@ class sr_stats(ctypes.Structure):
         ("owner_key", ctypes.c_uint32),
         ("balanced_levels", ctypes.c_uint32),
         ("table_encoding", ctypes.c_uint32),
+        ("root_path", ctypes.c_uint32),
+        ("reserved1", ctypes.c_uint32),
     ]
 
     def as_dict(self):

@@ -1585,6 +1585,7 @@ class DistEngine final : public EngineBase {
         head_undiscovered_ = (1u << M::NPROPS) - 1;
         const bool use_head = head_max_ > 0 && head_ok_ && T_ > 1;  // one partition: nothing to save
         const u64 per_part = hint / T_ + 1;
+        stats.root_path = use_head ? SR_ROOTS_HEAD : SR_ROOTS_PARTS;
 
         // ---- partitions: visited sets, arenas, level 0 ----
         const std::vector<u64> inits = init_states_of(m_);

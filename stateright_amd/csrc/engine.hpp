@@ -936,6 +936,7 @@ class Engine final : public EngineBase {
             slot_k_ = 0;
             slot_published_ = true;
             sq = next_seq();
+            stats.root_path = SR_ROOTS_INLINE;
             roots_start<M><<<1, 256, 0, stream_>>>(m_, view(), init, (u32)k, arena_.p, apar_.p, emask_ ? aeb_.p : nullptr,
                                                    emask_, lc_d_, reinterpret_cast<LevelCounters*>(slots_.p), SLOTS,
                                                    und0, hcd(sq), sq);
@@ -945,6 +946,7 @@ class Engine final : public EngineBase {
             init_counters();
             if (emask_) fill_u32<<<blocks_for(k, 64), 64, 0, stream_>>>(aeb_.p, (u32)k, emask_);  // bfs.rs:52-60
             sq = next_seq();
+            stats.root_path = k <= 256 ? SR_ROOTS_FUSED : SR_ROOTS_LAUNCHES;
             if (k <= 256) {
                 roots_fused<M><<<1, 256, 0, stream_>>>(m_, view(), arena_.p, (u32)k, lc_d_, und0, hcd(sq), sq);
             } else {

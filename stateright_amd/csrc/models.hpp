@@ -672,7 +672,7 @@ struct Ladder {
 };
 
 // -----------------------------------------------------------------------------------------------
-// Spread<W>(B, F, loops, mark): a test fixture (no reference counterpart) whose key width is a
+// Spread<W>(B, F, loops, mark[, roots, dup]): a test fixture (no reference counterpart) whose key width is a
 // parameter, so that a check can be put into any slot encoding of the visited set (kernels.hpp
 // make_table_view) whatever its size. A state is a subset x of F free bits, packed into a key of
 // B bits, F < B <= min(64 W, 128):
@@ -686,6 +686,12 @@ struct Ladder {
 // 2^F states, depth F, 1 + F 2^(F-1) + loops 2^F generated; level L holds C(F, L) states, each
 // generated by L parents. always "in range": the words are the packing of their own x (never
 // violated). sometimes "marked": x == mark.
+// Init states: the subsets 0 .. roots - 1 in that order, then 0 .. dup - 1 once more (duplicates,
+// which the reference counts, queues and expands again, bfs.rs:43-66); 1 <= roots <= 2^F,
+// 0 <= dup <= roots, roots + dup <= 512. The default (1, 0) is the single root x = 0. x = 0 is always
+// a root, so the reachable set is all 2^F subsets; generated = (roots + dup) + F 2^(F-1) + loops 2^F
+// + sum over i < dup of (F - popcount(i) + loops); depth = max over x of the fewest bits that x adds
+// to a root inside it (F - j for roots = 2^j).
 // -----------------------------------------------------------------------------------------------
 template <int W_>
 struct Spread {
@@ -693,6 +699,7 @@ struct Spread {
     static constexpr int W = W_, MW = 1, NPROPS = 2;
     int b, f, loops;
     u64 mark;
+    int roots = 1, dup = 0;
     int max_actions() const { return f + loops; }
     int max_out_degree() const { return f + loops; }
     SR_HD static u64 chunk(u64 x, int c) { return fmix64(x + 0x9E3779B97F4A7C15ull * (u64)(2 * c + 1)); }
@@ -728,8 +735,12 @@ struct Spread {
         for (int i = 0; i < W_; ++i) same &= t[i] == s[i];
         return !same;
     }
-    int init_count() const { return 1; }
-    int init_states(u64* out) const { pack(0, out); return 1; }
+    int init_count() const { return roots + dup; }
+    int init_states(u64* out) const {
+        for (int i = 0; i < roots; ++i) pack((u64)i, out + i * W_);
+        for (int i = 0; i < dup; ++i) pack((u64)i, out + (roots + i) * W_);
+        return roots + dup;
+    }
     int expectation(int p) const { return p == 0 ? ALWAYS : SOMETIMES; }
     const char* prop_name(int p) const { return p == 0 ? "in range" : "marked"; }
     int qkey_bits() const { return b; }

@@ -55,8 +55,8 @@ std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 
 std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
 std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4)
 
-// The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark), handed
-// to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip) validate alike.
+// The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark) and
+// optionally (roots, dup), its init states (default 1, 0), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip) validate alike.
 template <class F>
 auto with_spread_model(const i64* p, int np, F&& f) {
     if (np < 5) throw Error(SR_ERR_ARG, "spread needs 5 params (words, key_bits, free_bits, loops, mark)");
@@ -67,9 +67,14 @@ auto with_spread_model(const i64* p, int np, F&& f) {
         throw Error(SR_ERR_UNSUPPORTED, "spread: free_bits < key_bits <= min(64 words, 128)");
     if (loops < 0 || loops > 4) throw Error(SR_ERR_UNSUPPORTED, "spread: loops must be in 0..=4");
     if (mark < 0 || mark >> fb) throw Error(SR_ERR_ARG, "spread: mark must be below 2^free_bits");
-    if (w == 1) return f(Spread<1>{(int)b, (int)fb, (int)loops, (u64)mark});
-    if (w == 2) return f(Spread<2>{(int)b, (int)fb, (int)loops, (u64)mark});
-    return f(Spread<4>{(int)b, (int)fb, (int)loops, (u64)mark});
+    const i64 roots = np > 5 ? p[5] : 1, dup = np > 6 ? p[6] : 0;
+    if (np > 7) throw Error(SR_ERR_ARG, "spread takes at most 7 params (.., roots, dup)");
+    if (roots < 1 || roots > (i64)1 << fb) throw Error(SR_ERR_ARG, "spread: roots must be in 1..=2^free_bits");
+    if (dup < 0 || dup > roots) throw Error(SR_ERR_ARG, "spread: dup must be in 0..=roots");
+    if (roots + dup > 512) throw Error(SR_ERR_UNSUPPORTED, "spread: roots + dup must be at most 512");
+    if (w == 1) return f(Spread<1>{(int)b, (int)fb, (int)loops, (u64)mark, (int)roots, (int)dup});
+    if (w == 2) return f(Spread<2>{(int)b, (int)fb, (int)loops, (u64)mark, (int)roots, (int)dup});
+    return f(Spread<4>{(int)b, (int)fb, (int)loops, (u64)mark, (int)roots, (int)dup});
 }
 
 }  // namespace sr

@@ -275,7 +275,9 @@ class SimEngine final : public SimEngineBase {
         DBuf<u64> init_d;
         if ((u64)k * W <= ROOTS_INLINE_WORDS) {
             std::copy(inits_.begin(), inits_.end(), inl.w);
+            stats.root_path = SR_ROOTS_INLINE;
         } else {
+            stats.root_path = SR_ROOTS_BUFFER;
             init_d.alloc(o_.device, inits_.size());
             SR_HIP(hipMemcpyAsync(init_d.p, inits_.data(), inits_.size() * sizeof(u64), hipMemcpyHostToDevice, stream));
             a.inits = init_d.p;

@@ -198,14 +198,17 @@ class Spread(_Model):
     `free_bits` bits, packed with pseudo-random filler into a key of `key_bits` bits on `words` (1, 2
     or 4) words, so the key width, and with it the visited set's slot encoding, is a parameter.
     2**free_bits states, depth free_bits; `loops` (<= 4) further slots return the state itself without
-    the model reporting them as self-loops; `sometimes "marked"` holds at the subset `mark`."""
+    the model reporting them as self-loops; `sometimes "marked"` holds at the subset `mark`. The init
+    states are the subsets 0 .. roots-1 in that order, then 0 .. dup-1 once more (duplicates)."""
     MODEL_ID = N.SR_MODEL_SPREAD
 
-    def __init__(self, words, key_bits, free_bits, loops=0, mark=0):
+    def __init__(self, words, key_bits, free_bits, loops=0, mark=0, roots=1, dup=0):
         self.words, self.key_bits, self.free_bits, self.loops, self.mark = words, key_bits, free_bits, loops, mark
+        self.roots, self.dup = roots, dup
 
     def params(self):
-        return [self.words, self.key_bits, self.free_bits, self.loops, self.mark]
+        p = [self.words, self.key_bits, self.free_bits, self.loops, self.mark]
+        return p if (self.roots, self.dup) == (1, 0) else p + [self.roots, self.dup]
 
 
 class SingleCopyRegister(_Model):

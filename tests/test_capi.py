@@ -44,6 +44,19 @@ def test_struct_layouts():
     assert o.struct_size == ctypes.sizeof(_native.sr_opts)
 
 
+def test_stats_mirror_ends_with_the_root_path_word():
+    # sr_stats grew by root_path (+ a reserved word); the mirror lists the header's fields in order
+    from stateright_amd import _native
+    text = open(HEADER).read()
+    body = text[text.index("typedef struct sr_stats {"):text.index("} sr_stats;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(?:double|uint64_t|uint32_t)\s+([a-z0-9_]+);", body)
+    assert fields == [n for n, _ in _native.sr_stats._fields_] and fields[-2:] == ["root_path", "reserved1"]
+    assert ctypes.sizeof(_native.sr_stats) % 8 == 0
+    names = re.findall(r"\b(SR_ROOTS_[A-Z]+) = (\d+)", text)
+    assert names and all(getattr(_native, n) == int(v) for n, v in names)
+
+
 def test_spawn_without_device_fails_loudly():
     from stateright_amd import TwoPhaseSys, CheckerError
     from stateright_amd import _native

@@ -141,6 +141,42 @@ def test_chooser_is_uniform_over_the_enabled_slots():
         assert c > 0 and abs(c - n * p) <= 6 * sd, (s, c, n * p, sd)
 
 
+def test_init_draw_is_uniform_over_forty_init_states():
+    # 40 init nodes, each with a successor of its own: the first action names the init state drawn
+    roots = list(range(100, 140))
+    params = dgraph_params(SOMETIMES, [[r, r + 100] for r in roots])
+    n = 65536
+    counts = dict.fromkeys(roots, 0)
+    for i in range(n):
+        w = walk(N.SR_MODEL_DGRAPH, params, i, 1, nprops=1)
+        assert w["steps"] == 1
+        counts[w["actions"][0] - 100] += 1  # (a node that is no init state's successor is a KeyError)
+    p = 1 / len(roots)
+    sd = math.sqrt(n * p * (1 - p))
+    for r, c in counts.items():
+        assert c > 0 and abs(c - n * p) <= 6 * sd, (r, c, n * p, sd)
+
+
+def test_spread_walks_start_at_every_init_state_and_its_duplicates():
+    # W = 4, 10 init states and 2 duplicates (48 words of init states): a walk of depth 1 ends at its
+    # root plus one bit, and the duplicated roots 0 and 1 are drawn twice as often
+    params = [4, 78, 12, 0, 0, 10, 2]
+    n = 12000
+    started = dict.fromkeys(range(10), 0)
+    for i in range(n):
+        w = walk(N.SR_MODEL_SPREAD, params, i, 12, nprops=2)
+        bits = sum(1 << a for a in w["actions"])
+        assert bin(bits).count("1") == w["steps"] and w["end"] in (TERMINAL, DEPTH)
+        root = (2 ** 12 - 1) & ~bits if w["end"] == TERMINAL else None
+        if root is not None:
+            started[root] += 1
+    # depth 12 reaches the full set from every root but 0 (12 steps from 0 end at the depth limit)
+    assert started[0] == 0 and all(started[r] > 0 for r in range(1, 10))
+    sd = math.sqrt(n * (1 / 12) * (11 / 12))
+    assert abs(started[1] - n / 6) <= 6 * math.sqrt(n * (1 / 6) * (5 / 6))
+    assert all(abs(started[r] - n / 12) <= 6 * sd for r in range(2, 10))
+
+
 # ---- arguments ---------------------------------------------------------------------------------
 
 def test_bad_arguments_are_refused():
