@@ -899,6 +899,122 @@ struct ActionTable {
     }
 };
 
+// ---- Building blocks of the expanding and inserting kernels (expand_fast here; expand_route and
+// insert_records in kernels_dist.hpp). They take values and pointers, never a kernel's frame. ----
+
+// Appends the wave's new states of one round (nw: this lane has one, ns; mask = __ballot(nw), taken
+// by the caller, which may skip work for an empty round), aggregated per wave: ONE LDS atomic
+// reserves the wave's span of the workgroup's stage (stage_n may run past STAGE: the fill is
+// min(stage_n, STAGE)); what does not fit goes straight to the next frontier (next, next_par,
+// next_cap) with ONE claims atomic for the wave, never one per state: claims is a single address
+// that every wave of the GPU targets, and same-address atomics serialise at the L2 (~11 ns each,
+// scripts/microbench_atomics.hip). A staged state keeps spar in stage_par (null: no parent is
+// staged) and gets its parent word at the flush; a direct one gets par (P: the frontier's parent
+// word) and has its properties evaluated here (rank = position), past next_cap the level fails.
+// next and next_par are a frontier and its parent array, two allocations that never overlap.
+template <class M, class P>
+__device__ __forceinline__ void wave_append(const M& m, u64 mask, bool nw, const u64* ns, u32 spar, P par,
+                                            u64* stage, u32* stage_par, u32 STAGE, u32* stage_n,
+                                            u64* __restrict__ next, P* __restrict__ next_par, u32 next_cap,
+                                            LevelCounters* lc, u32 undiscovered) {
+    constexpr int W = M::W;
+    if (!mask) return;
+    const int lane = threadIdx.x & 63;
+    const u32 cnt = __popcll(mask);
+    const u32 below = __popcll(mask & ((1ull << lane) - 1));
+    const int leader = __builtin_ctzll(mask);
+    u32 sb = 0;
+    if (lane == leader) sb = atomicAdd(stage_n, cnt);
+    sb = lane_u32(sb, (u32)leader);
+    const u32 in_stage = sb >= STAGE ? 0u : min(cnt, STAGE - sb);
+    u32 gb = 0;
+    if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
+    gb = lane_u32(gb, (u32)leader);
+    if (!nw) return;
+    if (below < in_stage) {
+        const u32 kk = sb + below;
+#pragma unroll
+        for (int x = 0; x < W; ++x) stage[kk * W + x] = ns[x];
+        if (stage_par) stage_par[kk] = spar;
+    } else {
+        const u32 pos = gb + (below - in_stage);
+        if (pos < next_cap) {
+            store_state<W>(next, pos, ns);
+            next_par[pos] = par;
+        } else {
+            atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
+        }
+        eval_props(m, ns, pos, undiscovered, lc);
+    }
+}
+
+// The up to R keys a lane keeps in registers for probe_queue (kt[r]: slot value, kh[r]: home slot,
+// unused for a table that is always in fingerprint mode, FP_ONLY: there it is tag & mask; vmask bit
+// r: key r is probed).
+template <int R, bool FP_ONLY>
+struct ProbeKeys {
+    u64 kh[FP_ONLY ? 1 : R], kt[R];
+    u32 vmask = 0;
+};
+// The per-lane probe queue over a lane's ProbeKeys. One visited-set access per lane and iteration
+// (home load, linear-probe step or claim CAS), a lane moving to its next key as soon as one
+// resolves, so the wave's round trips are not each as long as its slowest lane's chain (DESIGN.md
+// §3 "probe loops"). Returns the mask of the keys that claimed a vacant slot (new states). STATS
+// counts the loads into *probes and the claims into *cas.
+template <int POL, bool STATS, int R, bool FP_ONLY>
+__device__ __forceinline__ u32 probe_queue(const TableView& t, ProbeKeys<R, FP_ONLY> k, u32* err,
+                                           u32* probes = nullptr, u32* cas = nullptr) {
+    u32 vmask = k.vmask;
+    u32 nmask = 0;
+    u32 st = 0, cr = 0, disp = 0;  // 0 idle, 1 load pending, 2 claim pending; its round
+    u64 si = 0, tag = 0;
+    const u64 step = probe_step(t);
+    for (;;) {
+        if (st == 0 && vmask) {
+            cr = (u32)__builtin_ctz(vmask);
+            vmask &= vmask - 1;
+            tag = k.kt[0];
+#pragma unroll
+            for (int r = 1; r < R; ++r)
+                if (cr == (u32)r) tag = k.kt[r];
+            if constexpr (FP_ONLY) {
+                si = tag & t.mask;
+            } else {
+                si = k.kh[0];
+#pragma unroll
+                for (int r = 1; r < R; ++r)
+                    if (cr == (u32)r) si = k.kh[FP_ONLY ? 0 : r];
+            }
+            st = 1;
+            disp = 0;
+        }
+        if (!__ballot(st != 0)) break;
+        u64 v = 0;
+        if (st == 1) v = slot_load<POL>(t, si);
+        if (st == 2) v = slot_cas(t, si, tag);
+        if constexpr (STATS) {
+            *probes += st == 1;
+            *cas += st == 2;
+        }
+        if (st != 0) {
+            if (v == tag) {
+                st = 0;  // visited already (or claimed by a concurrent duplicate)
+            } else if (v == 0) {
+                if (st == 2) nmask |= 1u << cr;  // our claim won
+                st = st == 1 ? 2u : 0u;
+            } else if (++disp >= t.plimit) {
+                atomicOr(err, (u32)ERR_TABLE_FULL);
+                st = 0;
+            } else {  // another key: the next slot
+                si = (si + 1) & t.mask;
+                tag += step;
+                st = 1;
+            }
+        }
+    }
+    return nmask;
+}
+
 // Diagnostic build only (SR_TIMELINE=1, scripts/build_timeline.sh): expand_fast's lane 0 of wave 0
 // stamps s_memrealtime (a 100 MHz clock shared by every CU) at each link of its workgroup's chain
 // of dependent round trips, after draining its memory counters, into g_timeline[launch seq % 64]
@@ -1220,9 +1336,7 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
         if (tl_first_chunk) SR_TL(11);
 #endif
 
-        // Appends the wave's new states of one round: one LDS atomic reserves the wave's span of the
-        // stage; what does not fit goes straight to the next frontier with ONE global atomic for the
-        // wave (never one per state).
+        // wave_append's text (above), inline: as a call it changed this kernel's registers
         auto append_new = [&](bool nw, const u64* ns, u32 par) {
             const u64 mask = __ballot(nw);
             if (!mask) return;
@@ -1355,6 +1469,7 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
 #if SR_TIMELINE
                 if (tl_first_round) SR_TL(4);
 #endif
+                // (probe_queue's text, above, inline: as a call it changed this kernel's registers)
                 u32 nmask = 0;  // bit r: round r's successor claimed a vacant slot (a new state)
                 u32 st = 0, cr = 0, disp = 0;  // 0 idle, 1 load pending, 2 claim pending; its round
                 u64 si = 0, tag = 0;
@@ -1505,9 +1620,7 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
             if (tl_first_round) SR_TL(5);
             tl_first_round = false;
 #endif
-            // Append the new states of this round, aggregated per wave: one LDS atomic reserves the
-            // wave's span of the stage; what does not fit goes straight to the next frontier with
-            // ONE global atomic for the wave (never one per state).
+            // the new states of this round: wave_append's text (above), inline as in append_new
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
                 const u64 mask = __ballot(nw[j]);

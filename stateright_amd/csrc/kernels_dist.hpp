@@ -408,12 +408,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M::W <
             constexpr int R = -PB;
             constexpr bool FP_ONLY = !has_qkey<M>::value;
             for (u32 s0 = w0; s0 < wend; s0 += 64u * R) {
-                u64 kh[FP_ONLY ? 1 : R], kt[R];
-                u32 vmask = 0;
+                ProbeKeys<R, FP_ONLY> pq;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    if (!FP_ONLY) kh[FP_ONLY ? 0 : r] = 0;
-                    kt[r] = 0;
+                    if (!FP_ONLY) pq.kh[FP_ONLY ? 0 : r] = 0;
+                    pq.kt[r] = 0;
                     const u32 i = s0 + (u32)r * 64u + (u32)lane;
                     u64 q[W];
                     bool ok = false, rem = false;
@@ -432,18 +431,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M::W <
                         if (ok) {
                             const ProbeKey pk = probe_key(m, t, q);
                             const u64 key = route_key(m, t, pk, q);
-                            if (fmask) {  // block-local duplicate filter (see expand_fast)
-                                const u64 old = atomicExch(reinterpret_cast<unsigned long long*>(&filt[filter_index(t, key) & fmask]),
-                                                           (unsigned long long)key);
-                                ok = old != key;
-                            }
+                            // block-local duplicate filter (see expand_fast; never the compact form)
+                            if (fmask) ok = !filter_seen(filt, false, filt_log2, fmask, t, key);
                             if (ok) {
                                 own = route_owner(m, t, q, key, nparts);
                                 rem = self_rec || own != my_part;
                                 if (!rem) {
-                                    vmask |= 1u << r;
-                                    kt[r] = pk.tag;
-                                    if (!FP_ONLY) kh[FP_ONLY ? 0 : r] = pk.home;
+                                    pq.vmask |= 1u << r;
+                                    pq.kt[r] = pk.tag;
+                                    if (!FP_ONLY) pq.kh[FP_ONLY ? 0 : r] = pk.home;
                                 }
                             }
                         }
@@ -490,49 +486,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M::W <
                     }
                 }
                 // the local successors' probes, one access per lane and iteration
-                u32 nmask = 0, st = 0, cr = 0, disp = 0;
-                u64 si = 0, tag = 0;
-                const u64 step = probe_step(t);
-                for (;;) {
-                    if (st == 0 && vmask) {
-                        cr = (u32)__builtin_ctz(vmask);
-                        vmask &= vmask - 1;
-                        tag = kt[0];
-#pragma unroll
-                        for (int r = 1; r < R; ++r)
-                            if (cr == (u32)r) tag = kt[r];
-                        if constexpr (FP_ONLY) {
-                            si = tag & t.mask;
-                        } else {
-                            si = kh[0];
-#pragma unroll
-                            for (int r = 1; r < R; ++r)
-                                if (cr == (u32)r) si = kh[FP_ONLY ? 0 : r];
-                        }
-                        st = 1;
-                        disp = 0;
-                    }
-                    if (!__ballot(st != 0)) break;
-                    u64 v = 0;
-                    if (st == 1) v = slot_load<0>(t, si);
-                    if (st == 2) v = slot_cas(t, si, tag);
-                    if (st != 0) {
-                        if (v == tag) {
-                            st = 0;
-                        } else if (v == 0) {
-                            if (st == 2) nmask |= 1u << cr;
-                            st = st == 1 ? 2u : 0u;
-                        } else if (++disp >= t.plimit) {
-                            atomicOr(&lc->err, (u32)ERR_TABLE_FULL);
-                            st = 0;
-                        } else {
-                            si = (si + 1) & t.mask;
-                            tag += step;
-                            st = 1;
-                        }
-                    }
-                }
-                // local new states -> the chunk's stage (their states recomputed from the map)
+                const u32 nmask = probe_queue<0, false>(t, pq, &lc->err);
+                // local new states -> the chunk's stage (their states recomputed from the map);
+                // wave_append's text, inline: as a call it changed this form's VGPR spills
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const bool nw = nmask >> r & 1;
@@ -605,13 +561,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M::W <
                 // cache off for a quotient-mode table)
                 pk[j] = ok[j] ? probe_key(m, t, ns[j]) : ProbeKey{0, 0};
                 key[j] = !ok[j] ? 0 : route_key(m, t, pk[j], ns[j]);
-                if (fmask && ok[j]) {  // block-local duplicate filter (see expand_fast)
-                    const u64 old = atomicExch(reinterpret_cast<unsigned long long*>(&filt[filter_index(t, key[j]) & fmask]),
-                                               (unsigned long long)key[j]);
-                    if (old == key[j]) {
-                        ++succ;
-                        ok[j] = false;
-                    }
+                // block-local duplicate filter (see expand_fast; never the compact form)
+                if (fmask && ok[j] && filter_seen(filt, false, filt_log2, fmask, t, key[j])) {
+                    ++succ;
+                    ok[j] = false;
                 }
                 own[j] = ok[j] ? route_owner(m, t, ns[j], key[j], nparts) : my_part;
                 rem[j] = ok[j] && (SELF || self_rec || own[j] != my_part);
@@ -647,38 +600,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M::W <
             }
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
-                const u64 pg = gid_base + wave0 + par[j];
-                // local new states -> the chunk's stage (one LDS atomic per wave)
-                const u64 mask = SELF ? 0ull : __ballot(nw[j]);
-                if (mask) {
-                    const u32 cnt = __popcll(mask);
-                    const u32 below = __popcll(mask & lanes_below);
-                    const int leader = __builtin_ctzll(mask);
-                    u32 sb = 0;
-                    if (lane == leader) sb = atomicAdd(&stage_n, cnt);
-                    sb = lane_u32(sb, (u32)leader);
-                    const u32 in_stage = sb >= (u32)STAGE ? 0u : min(cnt, (u32)STAGE - sb);
-                    u32 gb = 0;
-                    if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
-                    gb = lane_u32(gb, (u32)leader);
-                    if (nw[j]) {
-                        if (below < in_stage) {
-                            const u32 kk = sb + below;
-#pragma unroll
-                            for (int x = 0; x < W; ++x) stage[kk * W + x] = ns[j][x];
-                            stage_par[kk] = (u32)(wave0 + par[j]);
-                        } else {
-                            const u32 pos = gb + (below - in_stage);
-                            if (pos < next_cap) {
-                                store_state<W>(next, pos, ns[j]);
-                                next_par[pos] = pg;
-                            } else {
-                                atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
-                            }
-                            eval_props(m, ns[j], pos, undiscovered, lc);
-                        }
-                    }
-                }
+                // local new states -> the chunk's stage
+                wave_append(m, SELF ? 0ull : __ballot(nw[j]), nw[j], ns[j], (u32)(wave0 + par[j]), gid_base + wave0 + par[j],
+                            stage, stage_par, STAGE, &stage_n, next, next_par, next_cap, lc, undiscovered);
                 // remote records -> the chunk's record stage (one LDS atomic per wave)
                 const u64 rmask = __ballot(rem[j]);
                 if (!rmask) continue;
@@ -814,7 +738,6 @@ __device__ __forceinline__ void insert_records(const M& m, RecAt rec_at, u32 tot
                                                u64* next_par, u32 next_cap, LevelCounters* lc, u32 undiscovered,
                                                u64* stage, u32 STAGE, u32& stage_n, u32& base, u64& rsum) {
     constexpr int W = M::W;
-    const int lane = threadIdx.x & 63;
     auto flush = [&](u32 nl) {
         if (threadIdx.x == 0) base = atomicAdd(&lc->claims, nl);
         __syncthreads();
@@ -898,34 +821,9 @@ __device__ __forceinline__ void insert_records(const M& m, RecAt rec_at, u32 tot
                 }
             }
 #pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const bool nw = nws[j];
-                const u64 mask = __ballot(nw);
-                if (!mask) continue;
-                const u32 cnt = __popcll(mask), below = __popcll(mask & ((1ull << lane) - 1));
-                const int leader = __builtin_ctzll(mask);
-                u32 sb = 0;
-                if (lane == leader) sb = atomicAdd(&stage_n, cnt);
-                sb = lane_u32(sb, (u32)leader);
-                const u32 in_stage = sb >= STAGE ? 0u : min(cnt, STAGE - sb);
-                u32 gb = 0;
-                if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
-                gb = lane_u32(gb, (u32)leader);
-                if (!nw) continue;
-                if (below < in_stage) {
-#pragma unroll
-                    for (int x = 0; x < W; ++x) stage[(sb + below) * W + x] = ns[j][x];
-                } else {
-                    const u32 pos = gb + (below - in_stage);
-                    if (pos < next_cap) {
-                        store_state<W>(next, pos, ns[j]);
-                        next_par[pos] = PAR_SEARCH;
-                    } else {
-                        atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
-                    }
-                    eval_props(m, ns[j], pos, undiscovered, lc);
-                }
-            }
+            for (int j = 0; j < R; ++j)
+                wave_append(m, __ballot(nws[j]), nws[j], ns[j], 0u, PAR_SEARCH, stage, nullptr, STAGE, &stage_n, next, next_par,
+                            next_cap, lc, undiscovered);
             __syncthreads();
             const u32 sn = min(stage_n, STAGE);
             if (sn >= STAGE / 2) flush(sn);
@@ -963,34 +861,9 @@ __device__ __forceinline__ void insert_records(const M& m, RecAt rec_at, u32 tot
             if (ok[j] && cur[j] != pk[j].tag) find_or_claim_from(t, pk[j], cur[j], &nws[j], &lc->err);
         }
 #pragma unroll
-        for (int j = 0; j < PBI; ++j) {
-            const bool nw = nws[j];
-            const u64 mask = __ballot(nw);
-            if (!mask) continue;  // wave-aggregated: one LDS atomic, the overflow with one claims atomic per wave
-            const u32 cnt = __popcll(mask), below = __popcll(mask & ((1ull << lane) - 1));
-            const int leader = __builtin_ctzll(mask);
-            u32 sb = 0;
-            if (lane == leader) sb = atomicAdd(&stage_n, cnt);
-            sb = lane_u32(sb, (u32)leader);
-            const u32 in_stage = sb >= STAGE ? 0u : min(cnt, STAGE - sb);
-            u32 gb = 0;
-            if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
-            gb = lane_u32(gb, (u32)leader);
-            if (!nw) continue;
-            if (below < in_stage) {
-#pragma unroll
-                for (int x = 0; x < W; ++x) stage[(sb + below) * W + x] = ns[j][x];
-            } else {
-                const u32 pos = gb + (below - in_stage);
-                if (pos < next_cap) {
-                    store_state<W>(next, pos, ns[j]);
-                    next_par[pos] = PAR_SEARCH;
-                } else {
-                    atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
-                }
-                eval_props(m, ns[j], pos, undiscovered, lc);
-            }
-        }
+        for (int j = 0; j < PBI; ++j)
+            wave_append(m, __ballot(nws[j]), nws[j], ns[j], 0u, PAR_SEARCH, stage, nullptr, STAGE, &stage_n, next, next_par,
+                        next_cap, lc, undiscovered);
         __syncthreads();
         const u32 sn = min(stage_n, STAGE);  // the same value in every thread (no append until the next barrier)
         if (sn >= STAGE / 2) flush(sn);
