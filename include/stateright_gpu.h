@@ -269,7 +269,7 @@ void sr_gpu_bfs_free(sr_bfs* bfs);
  * fits no card still gets discoveries. What it does not prove: a run WITHOUT a discovery proves
  * nothing (sr_gpu_bfs_is_done is 1 only when every property was discovered).
  *
- * Determinism: trace w is a pure function of (model, seed, w, max_depth): a counter-based generator
+ * Determinism: trace w is a pure function of (model, seed, w, max_depth, loops): a counter-based generator
  * r(seed, w, t, k) (two rounds of murmur3's fmix64 over the seed, the trace index, the step t and
  * the attempt k) draws the init state and, per step, one of the enabled action slots; a slot whose
  * next state is None or outside the boundary is cleared and another is drawn; a state where none is
@@ -280,6 +280,20 @@ void sr_gpu_bfs_free(sr_bfs* bfs);
  * have run: a check is a deterministic function of (model, seed, walks, max_depth, batch size).
  * Per property the discovery is the hit of the fewest steps, ties to the lowest trace index; an
  * `eventually` property is hit only at a terminal state of a trace on which it never held.
+ *
+ * Loop detection (sr_sim_opts.loops = 1; off by default, and with it off nothing changes). A trace
+ * that returns to a state it has visited is a lasso, a prefix followed by a cycle that can repeat
+ * forever, so an `eventually` property that held nowhere on it is refuted without a terminal state
+ * (no fairness assumption, as the reference defines `eventually`). A trace keeps the fingerprints of
+ * its last 8 states and one checkpoint (taken at step 0 and at every power of two); at a state
+ * whose fingerprint equals one of them it ends with reason 4, its loop start being the index of that
+ * earlier state, and every `eventually` property that never held on it is hit there. Cycles of at
+ * most 8 states are found at their first closure; longer ones once the trace returns to a
+ * checkpoint. The trace with loops on is the trace with loops off, cut at its first detection
+ * (stateright_amd/csrc/sim.hpp has the full rule). The discovery path of such a hit is a lasso: its
+ * LAST state EQUALS its state at index loop start (both sides compare 64-bit fingerprints to end a
+ * trace, but a path is returned only after the two states were compared in full; a collision fails
+ * the call with SR_ERR_NONDETERMINISM and a message that says so).
  *
  * Every sr_gpu_bfs_* accessor works on the handle. unique_state_count is SET EQUAL to state_count
  * (states visited, repeats included: there is no visited set), max_depth is the longest trace in
@@ -298,16 +312,20 @@ typedef struct sr_sim_opts {
                                     (SR_ERR_ARG otherwise: a property may never be discovered)   */
     int32_t verbose;             /* one log line per batch on stderr                             */
     int32_t profile;             /* time every launch with HIP events                            */
+    int32_t loops;               /* 1 = loop detection (end reason 4, lasso discoveries); 0 = off */
 } sr_sim_opts;
 /* Zeroes the caller's mirror of `size` bytes (at most the library's own size) and sets struct_size
  * to what it wrote and max_depth to 4096. */
 void sr_sim_opts_init_sized(sr_sim_opts* opts, uint32_t size);
 /* Spawns the simulation; returns NULL on error (see sr_last_error). Non-blocking. */
 sr_bfs* sr_gpu_sim_spawn(int32_t model_id, const int64_t* params, int32_t nparams, const sr_sim_opts* opts);
-/* record_walks = 1: per trace, by trace index, its steps, end reason (1 terminal, 2 depth, 3 fault)
- * and the engine's fingerprint of its last state. Returns the number of traces run (at most cap are
+/* record_walks = 1: per trace, by trace index, its steps, end reason (1 terminal, 2 depth, 3 fault,
+ * 4 loop: only with sr_sim_opts.loops) and the engine's fingerprint of its last state. Returns the number of traces run (at most cap are
  * written), or SR_ERR_ARG for a handle that is no simulation. */
 int64_t sr_gpu_sim_walk_records(const sr_bfs* sim, uint32_t* steps, uint32_t* end_reason, uint64_t* final_fp, int64_t cap);
+/* record_walks = 1: per trace, by trace index, its loop start: the index (< its steps) of the earlier
+ * state a trace of end reason 4 returned to, 0xFFFFFFFF for every other trace. Returns as above. */
+int64_t sr_gpu_sim_walk_loop_starts(const sr_bfs* sim, uint32_t* loop_start, int64_t cap);
 /* The discovery of property `prop`: the trace index and the step of its hit. Returns 1, or 0 if the
  * property has no discovery (or the handle is no simulation). */
 int32_t sr_gpu_sim_hit(const sr_bfs* sim, int32_t prop, uint64_t* walk, uint32_t* step);
@@ -318,6 +336,12 @@ int32_t sr_gpu_sim_hit(const sr_bfs* sim, int32_t prop, uint64_t* walk, uint32_t
 int64_t sr_sim_walk(int32_t model_id, const int64_t* params, int32_t nparams, uint64_t seed, uint64_t walk,
                     uint32_t max_depth, int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp,
                     int32_t* first_hit_step, int32_t nprops, int32_t* attempts);
+/* sr_sim_walk with the loops flag of sr_sim_opts: loop_start (may be NULL) receives the trace's loop
+ * start, -1 unless its end reason is 4. */
+int64_t sr_sim_walk_loops(int32_t model_id, const int64_t* params, int32_t nparams, uint64_t seed, uint64_t walk,
+                          uint32_t max_depth, int32_t loops, int64_t* action_ids, int32_t cap, int32_t* end_reason,
+                          uint64_t* final_fp, int32_t* first_hit_step, int32_t nprops, int32_t* attempts,
+                          int32_t* loop_start);
 
 /* ---- Partitioned search over several GPUs (no counterpart in the reference,
  * which is single-process shared-memory: src/checker/bfs.rs:70-152) ----

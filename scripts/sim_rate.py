@@ -9,6 +9,11 @@ grid has lanes), the forms alternating run by run so that drift hits all alike, 
 range of steps/s and walks/s (steps = stats()["successors"], time = stats()["level_loop_sec"]: the
 batch loop, launches and the per-batch counter read-back included). As context it prints the host's
 single-thread rate of the same walks (sr_sim_walk over 10 000 walks). One JSON line at the end.
+
+--loops measures every form twice, without and with loop detection (detect_loops=True, rows named
+"<form>+loops"), all of them alternating in the same way: the cost of the mode is the ratio of a
+form's two rows (profiles/sim_loop_rate.txt). With loop detection the walks are other walks (each is
+cut at its first detected loop), so compare steps/s together with the steps and walks/s columns.
 """
 import argparse
 import json
@@ -30,10 +35,11 @@ MODELS = {
 }
 
 
-def run(model, seed, walks, depth, refill, grid):
+def run(model, seed, walks, depth, refill, grid, loops=False):
     os.environ["SR_SIM_REFILL"] = str(refill)  # both read when the engine is created
     os.environ["SR_SIM_GRID"] = str(grid)
-    c = model.checker().spawn_simulation(seed, walks=walks, max_depth=depth).join()
+    kw = {"detect_loops": True} if loops else {}  # (an A/B library of older sources has no such option)
+    c = model.checker().spawn_simulation(seed, walks=walks, max_depth=depth, **kw).join()
     st = c.stats()
     ran = c.state_count() - st["successors"]  # walks started
     return {"steps": st["successors"], "walks": ran, "sec": st["level_loop_sec"], "launches": st["expand_launches"],
@@ -51,6 +57,7 @@ def main():
     ap.add_argument("--host-walks", type=int, default=10_000)
     ap.add_argument("--grids", type=int, nargs="*", default=[0],
                     help="persistent form: grid caps in workgroups of 256 lanes to measure (0 = the engine's own cap)")
+    ap.add_argument("--loops", action="store_true", help="measure every form without and with loop detection")
     a = ap.parse_args()
     model = MODELS[a.model](a.n)
 
@@ -60,16 +67,18 @@ def main():
     print(f"host: {a.host_walks} walks, {hsteps} steps in {hsec:.3f} s: {hsteps / hsec:.3e} steps/s, "
           f"{a.host_walks / hsec:.3e} walks/s (one thread, through ctypes)")
 
-    forms = [("static", 0, 0)] + [("persistent" + (f"/{g}" if g else ""), 1, g) for g in a.grids]
-    for _, refill, grid in forms:  # warm-up: context, allocations, code objects
-        run(model, a.seed, a.walks, a.max_depth, refill, grid)
-    rows = {name: [] for name, _, _ in forms}
+    forms = [("static", 0, 0, False)] + [("persistent" + (f"/{g}" if g else ""), 1, g, False) for g in a.grids]
+    if a.loops:
+        forms = [f for name, refill, grid, _ in forms for f in ((name, refill, grid, False), (name + "+loops", refill, grid, True))]
+    for _, refill, grid, loops in forms:  # warm-up: context, allocations, code objects
+        run(model, a.seed, a.walks, a.max_depth, refill, grid, loops)
+    rows = {f[0]: [] for f in forms}
     for _ in range(a.repeats):
-        for name, refill, grid in forms:
-            rows[name].append(run(model, a.seed, a.walks, a.max_depth, refill, grid))
+        for name, refill, grid, loops in forms:
+            rows[name].append(run(model, a.seed, a.walks, a.max_depth, refill, grid, loops))
     out = {"model": a.model, "n": a.n, "walks": a.walks, "max_depth": a.max_depth, "repeats": a.repeats,
            "digest": N.build_digest(), "host_steps_per_s": hsteps / hsec}
-    for name, _, _ in forms:
+    for name, _, _, _ in forms:
         r = rows[name]
         sps = [x["steps"] / x["sec"] for x in r]
         wps = [x["walks"] / x["sec"] for x in r]

@@ -57,11 +57,14 @@ class sr_sim_opts(ctypes.Structure):
         ("target_state_count", ctypes.c_uint64),
         ("verbose", ctypes.c_int32),
         ("profile", ctypes.c_int32),
+        ("loops", ctypes.c_int32),
     ]
 
 
-# end reasons of a simulated walk (csrc/sim.hpp SimEnd)
+# end reasons of a simulated walk (csrc/sim.hpp SimEnd); SIM_LOOP only with loop detection
 SIM_TERMINAL, SIM_DEPTH, SIM_FAULT = 1, 2, 3
+SIM_LOOP = 4
+SIM_LOOP_WINDOW = 8
 
 
 class sr_stats(ctypes.Structure):
@@ -178,6 +181,11 @@ SIGNATURES = [
     ("sr_sim_walk", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                      _I64P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64),
                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("sr_gpu_sim_walk_loop_starts", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]),
+    ("sr_sim_walk_loops", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("sr_dist_unique_id", ctypes.c_int32, [ctypes.c_char_p]),
     ("sr_dist_init", _P, [ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     ("sr_dist_local_group", ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
@@ -283,24 +291,32 @@ def table_encoding(words, key_bits, slots):
     return dict(zip(("qbits", "dbits", "bbits", "plimit", "s32", "filter", "filter_log2", "min_cap_log2"), out))
 
 
-def sim_walk(model_id, params, seed, walk, max_depth=4096, nprops=32):
+def sim_walk(model_id, params, seed, walk, max_depth=4096, nprops=32, loops=False):
     """Walk `walk` of the simulation checker on the host (csrc/sim.hpp; no device needed), as the device
     runs it: dict(steps, end (SIM_TERMINAL / SIM_DEPTH / SIM_FAULT), final_fp, actions (canonical ids),
     first_hit (per property: the step of the walk's hit, -1 = none), attempts (drawn slots whose next
-    state was refused))."""
+    state was refused)). loops=True: with loop detection (end may be SIM_LOOP), and the dict gains
+    loop_start: the index of the earlier state a walk that ended SIM_LOOP returned to, -1 otherwise."""
     lib = load()
     params = list(params)
     arr = (ctypes.c_int64 * max(1, len(params)))(*params)
     acts = (ctypes.c_int64 * max(1, max_depth))()
-    end, att = ctypes.c_int32(), ctypes.c_int32()
+    end, att, start = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     fp = ctypes.c_uint64()
     hits = (ctypes.c_int32 * nprops)()
-    n = lib.sr_sim_walk(model_id, arr, len(params), seed, walk, max_depth, acts, max_depth, ctypes.byref(end),
-                        ctypes.byref(fp), hits, nprops, ctypes.byref(att))
+    if loops:
+        n = lib.sr_sim_walk_loops(model_id, arr, len(params), seed, walk, max_depth, 1, acts, max_depth, ctypes.byref(end),
+                                  ctypes.byref(fp), hits, nprops, ctypes.byref(att), ctypes.byref(start))
+    else:
+        n = lib.sr_sim_walk(model_id, arr, len(params), seed, walk, max_depth, acts, max_depth, ctypes.byref(end),
+                            ctypes.byref(fp), hits, nprops, ctypes.byref(att))
     if n < 0:
         raise ValueError(f"sr_sim_walk: {last_error()} (status {n})")
-    return {"steps": n, "end": end.value, "final_fp": fp.value, "actions": list(acts[:n]), "first_hit": list(hits),
-            "attempts": att.value}
+    out = {"steps": n, "end": end.value, "final_fp": fp.value, "actions": list(acts[:n]), "first_hit": list(hits),
+           "attempts": att.value}
+    if loops:
+        out["loop_start"] = start.value
+    return out
 
 
 def runtime_versions():

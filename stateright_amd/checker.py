@@ -228,13 +228,21 @@ class CheckerBuilder:
         self._opts.order = N.SR_ORDER_FAST
         return self.spawn_bfs()
 
-    def spawn_simulation(self, seed, walks=None, max_depth=4096, record_walks=False):
+    def spawn_simulation(self, seed, walks=None, max_depth=4096, record_walks=False, detect_loops=False):
         """The simulation checker (Stateright's `spawn_simulation`, added after the 0.28 mirrored here):
         `walks` independent random traces of at most `max_depth` steps from the init states, one GPU
         lane per trace, the properties evaluated on every state. No visited set is kept, so a model
         too large for `spawn_bfs` still gets discoveries; a run without a discovery proves nothing.
 
-        Trace w is a pure function of (model, seed, w, max_depth) (csrc/sim.hpp), and the check stops
+        detect_loops=True (off by default; with it off nothing changes) also ends a trace where it
+        returns to a state it has visited (end reason 4): such a trace is a lasso, a prefix and a cycle
+        that can repeat forever, so an `eventually` property that held nowhere on it is discovered
+        without a terminal state, which neither the plain traces nor `spawn_bfs` can report. Cycles of
+        at most 8 states are found at their first closure, longer ones once the trace returns to a
+        checkpoint taken at a power-of-two step; the discovery's path ends at the state it repeats
+        (`GpuSimulationChecker.loop_start`). No fairness is assumed.
+
+        Trace w is a pure function of (model, seed, w, max_depth, detect_loops) (csrc/sim.hpp), and the check stops
         after the first whole batch of traces at whose end every property is discovered,
         `target_state_count` is reached or `walks` traces have run. walks=None needs a
         `target_state_count` (a property may never be discovered). Honours `device`,
@@ -262,6 +270,7 @@ class CheckerBuilder:
         so.target_state_count = self._opts.target_state_count
         so.verbose = self._opts.verbose
         so.profile = self._opts.profile
+        so.loops = int(bool(detect_loops))
         if walks is not None and so.walks == 0:
             raise ValueError("spawn_simulation: walks must be positive")
         return GpuSimulationChecker(self._model, so)
@@ -607,7 +616,9 @@ class GpuSimulationChecker(GpuBfsChecker):
     `state_count` is the number of states the walks visited, `unique_state_count` EQUALS it (there is
     no visited set: repeats count), `max_depth` is the longest walk in steps, and `is_done` means
     "every property discovered", so `assert_no_discovery` / `assert_properties` of a property that is
-    never violated report that model checking is incomplete: a run without a discovery proves nothing."""
+    never violated report that model checking is incomplete: a run without a discovery proves nothing.
+    With `detect_loops=True` the discovery of an `eventually` property may be a lasso (`loop_start`),
+    which `assert_discovery` then accepts."""
 
     def __init__(self, model, sim_opts):
         lib = N.load()
@@ -623,7 +634,7 @@ class GpuSimulationChecker(GpuBfsChecker):
 
     def walk_records(self):
         """record_walks=True: [(steps, end reason, fingerprint of the last state)] per walk, by walk
-        index (end reason: 1 terminal, 2 depth, 3 fault)."""
+        index (end reason: 1 terminal, 2 depth, 3 fault, 4 loop)."""
         n = self._lib.sr_gpu_sim_walk_records(self._h, None, None, None, 0)
         if n < 0:
             raise CheckerError("sr_gpu_sim_walk_records", n)
@@ -656,6 +667,57 @@ class GpuSimulationChecker(GpuBfsChecker):
         return step.value, walk.value
 
     def host_walk(self, i):
-        """Walk `i` of this check re-walked on the host (`_native.sim_walk`)."""
+        """Walk `i` of this check re-walked on the host (`_native.sim_walk`), in this check's mode."""
         return N.sim_walk(self._model.MODEL_ID, self._params, self._sim_opts.seed, i, self._sim_opts.max_depth,
-                          max(1, len(self.properties())))
+                          max(1, len(self.properties())), loops=bool(self._sim_opts.loops))
+
+    def walk_loop_starts(self):
+        """record_walks=True: per walk, by walk index, its loop start as a numpy int64 array: the index
+        of the earlier state a walk that ended with reason 4 returned to, -1 for every other walk."""
+        import numpy as np
+        n = self._lib.sr_gpu_sim_walk_loop_starts(self._h, None, 0)
+        if n < 0:
+            raise CheckerError("sr_gpu_sim_walk_loop_starts", n)
+        start = np.zeros(max(1, n), dtype=np.uint32)
+        self._lib.sr_gpu_sim_walk_loop_starts(self._h, start.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n)
+        out = start[:n].astype(np.int64)
+        out[out == 0xFFFFFFFF] = -1
+        return out
+
+    def loop_start(self, name):
+        """detect_loops=True: if the discovery of the `eventually` property `name` is a lasso, the index
+        of the path's state that its last state repeats; None otherwise (no discovery, another kind
+        of property, or a path that ends at a terminal state)."""
+        h = self.hit(name)
+        if h is None or not self._sim_opts.loops or self.properties()[self._prop_index(name)][1] != Expectation.Eventually:
+            return None
+        step, walk = h
+        w = self.host_walk(walk)
+        return w["loop_start"] if w["end"] == N.SIM_LOOP and w["steps"] == step else None
+
+    def assert_discovery(self, name, actions):
+        """As the base class's, and with detect_loops=True an `eventually` property also accepts a
+        lasso: a path on which the property never holds and which ends at a terminal state OR at a
+        state equal to an earlier state of the path (the cycle between them can repeat forever)."""
+        i = self._prop_index(name)
+        if not self._sim_opts.loops or self.properties()[i][1] != Expectation.Eventually:
+            return super().assert_discovery(name, actions)
+        found = self.assert_any_discovery(name)
+        info = []
+        for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):
+            r = self.replay_trace(actions, init)
+            if r is None:
+                continue
+            per_state, terminal = r
+            states, _ = self.replay(actions, init)
+            closed = states[-1] in states[:-1]
+            satisfied = any(s[i] for s in per_state)
+            if not satisfied and (terminal or closed):
+                return
+            if satisfied:
+                info.append("incorrect counterexample satisfies eventually property")
+            if not (terminal or closed):
+                info.append("incorrect counterexample is nonterminal and closes no loop")
+        extra = f" ({'; '.join(info)})" if info else ""
+        raise AssertionError(f'Invalid discovery for "{name}"{extra}, but a valid one was found. '
+                             f"found={found.into_actions()}")

@@ -540,6 +540,15 @@ int64_t sr_gpu_sim_walk_records(const sr_bfs* b, uint32_t* steps, uint32_t* end_
     return e->sim_records(steps, end_reason, final_fp, std::max<int64_t>(cap, 0));
 }
 
+int64_t sr_gpu_sim_walk_loop_starts(const sr_bfs* b, uint32_t* loop_start, int64_t cap) {
+    const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
+    if (!e) {
+        set_error("not a simulation handle");
+        return SR_ERR_ARG;
+    }
+    return e->sim_loop_starts(loop_start, std::max<int64_t>(cap, 0));
+}
+
 int32_t sr_gpu_sim_hit(const sr_bfs* b, int32_t prop, uint64_t* walk, uint32_t* step) {
     const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
     return e && e->sim_hit(prop, walk, step) ? 1 : 0;
@@ -548,17 +557,25 @@ int32_t sr_gpu_sim_hit(const sr_bfs* b, int32_t prop, uint64_t* walk, uint32_t* 
 int64_t sr_sim_walk(int32_t model, const int64_t* p, int32_t np, uint64_t seed, uint64_t walk, uint32_t max_depth,
                     int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp, int32_t* first_hit_step,
                     int32_t nprops, int32_t* attempts) {
+    return sr_sim_walk_loops(model, p, np, seed, walk, max_depth, 0, action_ids, cap, end_reason, final_fp, first_hit_step, nprops,
+                             attempts, nullptr);
+}
+
+int64_t sr_sim_walk_loops(int32_t model, const int64_t* p, int32_t np, uint64_t seed, uint64_t walk, uint32_t max_depth,
+                          int32_t loops, int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp,
+                          int32_t* first_hit_step, int32_t nprops, int32_t* attempts, int32_t* loop_start) {
     try {
         if (!max_depth || max_depth > SIM_MAX_DEPTH) throw Error(SR_ERR_ARG, "simulation: max_depth must be in 1..=2^20");
         if (walk >= SIM_MAX_WALKS) throw Error(SR_ERR_ARG, "simulation: walk must be below 2^40");
         const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
             using M = std::decay_t<decltype(m)>;
-            const SimHostWalk h = sim_host_walk(m, seed, walk, max_depth);
+            const SimHostWalk h = sim_host_walk(m, seed, walk, max_depth, loops != 0);
             for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
             if (end_reason) *end_reason = (int32_t)h.end;
             if (final_fp) *final_fp = h.final_fp;
             for (int32_t q = 0; first_hit_step && q < nprops; ++q) first_hit_step[q] = q < M::NPROPS ? h.first_hit[q] : -1;
             if (attempts) *attempts = (int32_t)h.redraws;
+            if (loop_start) *loop_start = h.end == SIM_LOOP ? (int32_t)h.loop_start : -1;
             return (i64)h.steps;
         });
         if (r == SR_ERR_UNSUPPORTED) set_error("sr_sim_walk: model " + std::to_string(model) + " has no host form");

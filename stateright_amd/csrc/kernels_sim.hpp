@@ -1,8 +1,11 @@
-// The simulation checker's kernel (gfx950): simulate_walks<M> runs one batch of random walks, the
+// The simulation checker's kernel (gfx950): simulate_walks<M, REFILL, LOOPS> runs one batch of random walks, the
 // walks of consecutive indices [b0, b0 + n), with the walk defined in sim.hpp (this header is
 // included from there, after that definition).
 //
-// One lane carries one walk with its state in registers (W words); no LDS, no visited set. Results
+// One lane carries one walk with its state in registers (W words); no LDS, no visited set. With
+// loop detection (LOOPS = true, sim.hpp "Loop detection") a lane also keeps the checkpoint in
+// registers and the window of its last 8 fingerprints in LDS (SimRingLds below); the LOOPS = false
+// instantiations hold none of that code. Results
 // are keyed by the walk index, never by lane or wave, so both forms below give the same per-walk
 // records and the same hits:
 //   static form (REFILL = false): lane g of the grid walks index b0 + g, and a wave runs as long as
@@ -27,14 +30,15 @@ constexpr u32 SIM_BLOCK = 256;
 constexpr u32 SIM_PERSIST_WAVES = 16;  // persistent form: waves per compute unit
 
 struct alignas(16) SimRecord {  // record_walks: one per walk, at index w - b0
-    u32 steps, end;
-    u64 fp;  // state_fp<M> of the walk's last state
+    u32 steps;
+    u32 end;  // the SimEnd in the low byte; SIM_LOOP: loop_start (<= 2^20) in the bits above it
+    u64 fp;   // state_fp<M> of the walk's last state
 };
 static_assert(sizeof(SimRecord) == 16, "one 16-byte store per record");
 
 struct alignas(128) SimShard {
     u64 states;    // states visited
-    u64 ended[4];  // walks ended, by SimEnd
+    u64 ended[SIM_ENDS];  // walks ended, by SimEnd
     u32 longest;   // the longest walk, in steps
 };
 struct SimDevice {
@@ -63,7 +67,19 @@ __device__ __forceinline__ u32 sim_wave_max(u32 v) {
     return v;
 }
 
-template <class M, bool REFILL>
+// The window of a lane's loop memory (sim.hpp SimLoops): the workgroup's LDS, laid out
+// ring[slot][thread], 8 x 256 x 8 B = 16 KiB. A wave's 8-byte access at one slot covers 512
+// consecutive bytes, and a slot is 2 KiB (a multiple of the 256-byte bank row), so lanes at
+// different slots (the persistent form: different t) keep their own banks too: no conflict in the
+// 32-lane groups of a 64-bit read or the 16-lane groups of a 64-bit write. 16 KiB per workgroup of
+// four waves leaves the wave limit of a compute unit (32 waves: 128 KiB) inside its 160 KiB.
+struct SimRingLds {
+    u64* lane;  // &ring[0][threadIdx.x]
+    __device__ __forceinline__ u64 get(u32 slot) const { return lane[slot * SIM_BLOCK]; }
+    __device__ __forceinline__ void put(u32 slot, u64 v) { lane[slot * SIM_BLOCK] = v; }
+};
+
+template <class M, bool REFILL, bool LOOPS>
 __global__ void __launch_bounds__(SIM_BLOCK) simulate_walks(M m, SimArgs a, InlineStates inl) {
     constexpr u32 NONE = ~0u;
     const u32 lane = threadIdx.x & 63;
@@ -80,6 +96,12 @@ __global__ void __launch_bounds__(SIM_BLOCK) simulate_walks(M m, SimArgs a, Inli
     int pend_src = 0;
     u64 c_states = 0;
     u32 c_term = 0, c_depth = 0, c_fault = 0, c_longest = 0;
+    u32 c_loop = 0;
+    std::conditional_t<LOOPS, SimLoops<SimRingLds>, SimNoLoops> lp;
+    if constexpr (LOOPS) {
+        __shared__ u64 ring[SIM_LOOP_WINDOW][SIM_BLOCK];
+        lp.ring.lane = &ring[0][threadIdx.x];  // (never cleared: a walk reads only what it wrote, by its own t)
+    }
 
     // Bounded: every pass either advances a walk (at most max_depth + 1 passes each), starts one, or
     // lands a reservation; the batch has n walks and a lane reserves past n at most once.
@@ -120,16 +142,21 @@ __global__ void __launch_bounds__(SIM_BLOCK) simulate_walks(M m, SimArgs a, Inli
                     if (key < __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
                         atomicMin(best, (unsigned long long)key);
                 },
-                [](const u64*, int) {});
+                [](const u64*, int) {}, lp);
             if (e != SIM_RUNNING) {
                 c_term += e == SIM_TERMINAL;
                 c_depth += e == SIM_DEPTH;
                 c_fault += e == SIM_FAULT;
+                u32 endw = e;
+                if constexpr (LOOPS) {
+                    c_loop += e == SIM_LOOP;
+                    if (e == SIM_LOOP) endw |= lp.start << 8;
+                }
                 c_longest = max(c_longest, wk.t);
                 if (a.records) {
                     const u64 fp = state_fp<M>(wk.s);
                     ulonglong2 r;
-                    r.x = (u64)wk.t | (u64)e << 32;
+                    r.x = (u64)wk.t | (u64)endw << 32;
                     r.y = fp;
                     *reinterpret_cast<ulonglong2*>(&a.records[cur]) = r;  // cur < n: one 16-byte store
                 }
@@ -142,12 +169,17 @@ __global__ void __launch_bounds__(SIM_BLOCK) simulate_walks(M m, SimArgs a, Inli
     const u64 s_states = sim_wave_sum(c_states);
     const u64 s_term = sim_wave_sum(c_term), s_depth = sim_wave_sum(c_depth), s_fault = sim_wave_sum(c_fault);
     const u32 s_longest = sim_wave_max(c_longest);
+    u64 s_loop = 0;
+    if constexpr (LOOPS) s_loop = sim_wave_sum(c_loop);
     if (lane == 0 && s_states) {
         SimShard* sh = &a.dev->shard[blockIdx.x % NSHARD];
         atomicAdd((unsigned long long*)&sh->states, (unsigned long long)s_states);
         if (s_term) atomicAdd((unsigned long long*)&sh->ended[SIM_TERMINAL], (unsigned long long)s_term);
         if (s_depth) atomicAdd((unsigned long long*)&sh->ended[SIM_DEPTH], (unsigned long long)s_depth);
         if (s_fault) atomicAdd((unsigned long long*)&sh->ended[SIM_FAULT], (unsigned long long)s_fault);
+        if constexpr (LOOPS) {
+            if (s_loop) atomicAdd((unsigned long long*)&sh->ended[SIM_LOOP], (unsigned long long)s_loop);
+        }
         atomicMax(&sh->longest, s_longest);
     }
 }

@@ -6,7 +6,8 @@
 // The walk is defined ONCE here, as SR_HD templates over a GpuModel M (models.hpp): the kernel
 // (kernels_sim.hpp simulate_walks) and the host re-walk (sim_host_walk: discovery paths, the
 // host-only sr_sim_walk entry point) instantiate the same code, so a walk is a pure function of
-// (model, seed, walk index w, max_depth), on either side.
+// (model, seed, walk index w, max_depth, loops), on either side (loops: the opt-in loop detection
+// below; off by default).
 //
 // Randomness (part of the definition). A counter-based generator, no per-lane state:
 //   sim_walk_key(seed, w) = fmix64(seed + 0x9E3779B97F4A7C15 * (w + 1))
@@ -35,6 +36,33 @@
 // EvBits<M> are not simulated. Every loop is bounded: steps by max_depth (<= 2^20), redraws by the
 // number of enabled slots (<= max_actions).
 //
+// Loop detection (opt-in: sr_sim_opts.loops, `spawn_simulation(detect_loops=True)`). A trace is a
+// path, so a trace that returns to a state it has visited is a lasso: a finite prefix and a cycle that
+// can repeat forever. If an `eventually` property held nowhere on it, that infinite execution refutes
+// the property (as the reference defines `eventually`: no fairness assumption), which neither the
+// plain walk nor BFS can report (src/checker.rs:400-413, the FIXME's [0, 2, 4, 2]). With loops on a
+// walk also keeps a loop memory of fingerprints f_i = state_fp<M>(s_i):
+//   window:     the fingerprints of the last min(t, R) states before s_t, R = SIM_LOOP_WINDOW = 8;
+//   checkpoint: a pair (f_c, t_c), initially (f_0, 0).
+// Visiting s_t gains one step, after the property visit and the `faulted` test and BEFORE the
+// t == max_depth test. For t >= 1: let j be the largest index in the window with f_j == f_t; failing
+// that, j = t_c if f_c == f_t. If there is such a j the walk ends at s_t with SIM_LOOP and
+// loop_start = j, and every `eventually` property not in `sat` is a hit (p, t, w), exactly as at a
+// terminal state. Otherwise f_t enters the window, and if t is a power of two the checkpoint
+// becomes (f_t, t). So:
+//   a cycle of length <= 8, self-loops included, is reported at its first closure, with the
+//     shortest lasso;
+//   a longer cycle is reported once the walk returns to a checkpoint: a checkpoint taken at 2^k is
+//     held for 2^k steps, so in a finite recurrent component that happens with probability 1 as the
+//     depth grows (a deterministic lasso of prefix mu and cycle length L > 8 ends at the first
+//     t = 2^k + L with 2^k >= max(mu, L), j = 2^k: L = 12, mu <= 16 gives (t, j) = (28, 16));
+//   the generator is counter-based and the loop memory feeds nothing back into the walk, so the
+//     loop-mode walk w is exactly the plain walk w cut at its first detection;
+//   a walk that closed a loop has nothing new to show on it, and its lane is free for another walk.
+// Fingerprints are compared, not states: the device and sim_host_walk may end a walk on a
+// collision of two 64-bit fingerprints, but a discovery path is only returned after s_j and s_t
+// were compared word for word (SimEngine::discovery_walk fails the call otherwise).
+//
 // A check (SimEngine) runs the walks 0 .. walks-1 in batches of consecutive indices, one launch per
 // batch, and stops after the first WHOLE batch at whose end every property has a hit, state_count
 // reached target_state_count, or the walks are exhausted; so a check is a deterministic function of
@@ -47,7 +75,9 @@
 
 namespace sr {
 
-enum SimEnd : u32 { SIM_RUNNING = 0, SIM_TERMINAL = 1, SIM_DEPTH = 2, SIM_FAULT = 3 };
+enum SimEnd : u32 { SIM_RUNNING = 0, SIM_TERMINAL = 1, SIM_DEPTH = 2, SIM_FAULT = 3, SIM_LOOP = 4, SIM_ENDS = 5 };
+constexpr u32 SIM_LOOP_WINDOW = 8;  // a power of two: slot t % SIM_LOOP_WINDOW holds f_t
+constexpr u32 SIM_NO_LOOP = ~0u;
 constexpr u32 SIM_K_INIT = 0xFFFFFFFFu;
 constexpr u32 SIM_MAX_DEPTH = 1u << 20;
 constexpr u64 SIM_MAX_WALKS = 1ull << 40;
@@ -101,12 +131,33 @@ SR_HD int sim_select(const u64* mask, u32 j) {
     return a;
 }
 
+// The loop memory of a walk (loop detection on). Ring stores the window: get(slot) / put(slot, f)
+// over SIM_LOOP_WINDOW slots, an array on the host (SimRingArray), a view of the workgroup's LDS in
+// the kernel (kernels_sim.hpp SimRingLds). Nothing is reset between walks: the valid slots are
+// derived from the walk's own t, so a lane that takes a new walk never reads its predecessor's.
+struct SimRingArray {
+    u64 f[SIM_LOOP_WINDOW] = {};
+    SR_HD u64 get(u32 slot) const { return f[slot]; }
+    SR_HD void put(u32 slot, u64 v) { f[slot] = v; }
+};
+template <class Ring>
+struct SimLoops {
+    static constexpr bool on = true;
+    Ring ring;
+    u64 cf = 0;                // checkpoint: f_c
+    u32 ct = 0;                //             t_c
+    u32 start = SIM_NO_LOOP;   // loop_start of a walk that ended with SIM_LOOP
+};
+struct SimNoLoops {  // loop detection off: sim_advance compiles to the plain walk
+    static constexpr bool on = false;
+};
+
 // Visits s_t and takes one step. emask: the model's `eventually` properties (the others are reported
 // where discovers() holds). on_hit(p, t) is called for every hit of the walk; on_step(s_t, a)
-// before the walk moves on through slot a.
+// before the walk moves on through slot a. lp: SimLoops<Ring> or SimNoLoops.
 // Returns SIM_RUNNING (wk now holds s_{t+1}) or the reason the walk ended at s_t.
-template <class M, class Hit, class Step>
-SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step) {
+template <class M, class Hit, class Step, class Loops>
+SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step, Loops& lp) {
 #pragma unroll
     for (int p = 0; p < M::NPROPS; ++p) {
         if (emask >> p & 1) {
@@ -118,6 +169,26 @@ SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&
     }
     if constexpr (has_faulted<M>::value) {
         if (m.faulted(wk.s)) return SIM_FAULT;
+    }
+    if constexpr (Loops::on) {
+        const u64 f = state_fp<M>(wk.s);
+        const u32 t = wk.t;
+        u32 j = t && lp.cf == f ? lp.ct : SIM_NO_LOOP;
+        // the window, oldest first, so that the largest index wins (no early exit: every read is
+        // independent of the others); t = 0 has none, and its fingerprint is the first checkpoint
+#pragma unroll
+        for (u32 i = SIM_LOOP_WINDOW; i; --i)
+            if (i <= t && lp.ring.get((t - i) % SIM_LOOP_WINDOW) == f) j = t - i;
+        if (j != SIM_NO_LOOP) {
+            lp.start = j;
+            for (u32 e = emask & ~wk.sat; e; e &= e - 1) on_hit(__builtin_ctz(e), t);
+            return SIM_LOOP;
+        }
+        lp.ring.put(t % SIM_LOOP_WINDOW, f);
+        if ((t & (t - 1)) == 0) {  // t = 0 and the powers of two
+            lp.cf = f;
+            lp.ct = t;
+        }
     }
     if (wk.t >= max_depth) return SIM_DEPTH;
     u64 mask[M::MW];
@@ -153,17 +224,20 @@ namespace sr {
 // One walk on the host, as the device runs it.
 struct SimHostWalk {
     u32 steps = 0, end = SIM_RUNNING, redraws = 0;
+    u32 loop_start = SIM_NO_LOOP;  // end == SIM_LOOP: the index of the earlier state the walk returned to
     u64 final_fp = 0;
     std::vector<i64> actions;   // canonical action ids, one per step
     std::vector<i64> states;    // (steps + 1) descriptions (only when asked for)
+    std::vector<u64> words;     // (steps + 1) states as the engine holds them, W words each (likewise)
     std::vector<u64> fps;       // (steps + 1) fingerprints (only when asked for)
     std::vector<int> first_hit; // per property: the step of its hit, -1 = none
 };
 
 // The whole walk w. describe: also the descriptions and fingerprints of its first keep + 1 states and
 // the action ids of its first keep steps (a discovery path is the walk cut at its hit's step).
+// loops: with loop detection.
 template <class M>
-SimHostWalk sim_host_walk(const M& m, u64 seed, u64 w, u32 max_depth, bool describe = false, u32 keep = ~0u) {
+SimHostWalk sim_host_walk(const M& m, u64 seed, u64 w, u32 max_depth, bool loops, bool describe = false, u32 keep = ~0u) {
     const std::vector<u64> inits = init_states_of(m);
     const u32 k = (u32)(inits.size() / M::W);
     if (!k) throw Error(SR_ERR_ARG, "simulation: the model has no init state");
@@ -178,17 +252,22 @@ SimHostWalk sim_host_walk(const M& m, u64 seed, u64 w, u32 max_depth, bool descr
         const size_t o = r.states.size();
         r.states.resize(o + wd);
         m.describe(s, &r.states[o]);
+        r.words.insert(r.words.end(), s, s + M::W);
         r.fps.push_back(state_fp<M>(s));
     };
+    SimLoops<SimRingArray> lp;
+    SimNoLoops none;
     for (;;) {
         const u32 t = wk.t;
-        r.end = sim_advance(m, wk, max_depth, emask, [&](int p, u32 th) { if (r.first_hit[p] < 0) r.first_hit[p] = (int)th; },
-                            [&](const u64* s, int a) {
-                                emit(s, t);
-                                if (t < keep) r.actions.push_back(m.action_id(s, a));
-                            });
+        auto on_hit = [&](int p, u32 th) { if (r.first_hit[p] < 0) r.first_hit[p] = (int)th; };
+        auto on_step = [&](const u64* s, int a) {
+            emit(s, t);
+            if (t < keep) r.actions.push_back(m.action_id(s, a));
+        };
+        r.end = loops ? sim_advance(m, wk, max_depth, emask, on_hit, on_step, lp) : sim_advance(m, wk, max_depth, emask, on_hit, on_step, none);
         if (r.end != SIM_RUNNING) break;
     }
+    if (r.end == SIM_LOOP) r.loop_start = lp.start;
     emit(wk.s, wk.t);
     r.steps = wk.t;
     r.redraws = wk.redraws;
@@ -201,6 +280,7 @@ class SimEngineBase : public EngineBase {
   public:
     virtual bool sim_hit(int p, u64* walk, u32* step) const = 0;
     virtual i64 sim_records(u32* steps, u32* end, u64* fp, i64 cap) const = 0;
+    virtual i64 sim_loop_starts(u32* start, i64 cap) const = 0;
 };
 
 // SR_SIM_REFILL: 1 = the persistent form (a lane whose walk ended takes the next unstarted index of
@@ -296,7 +376,7 @@ class SimEngine final : public SimEngineBase {
         SR_HIP(hipDeviceGetAttribute(&ndev, hipDeviceAttributeMultiprocessorCount, o_.device));
         if (ndev <= 0) ndev = 256;
 
-        u64 states = 0, started = 0, ended[4] = {0, 0, 0, 0};
+        u64 states = 0, started = 0, ended[SIM_ENDS] = {};
         u32 longest = 0;
         const auto t_loop = Clock::now();
         std::vector<SimDevice> host(1);
@@ -314,8 +394,10 @@ class SimEngine final : public SimEngineBase {
             if (refill_) grid = std::min<u32>(grid, grid_cap_ ? grid_cap_ : (u32)ndev * SIM_PERSIST_WAVES / (SIM_BLOCK / 64));
             const size_t ev = 2 * stats.expand_launches;
             if (o_.profile) SR_HIP(hipEventRecord(lease.c->event(ev), stream));
-            if (refill_) simulate_walks<M, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
-            else simulate_walks<M, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            if (o_.loops && refill_) simulate_walks<M, true, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else if (o_.loops) simulate_walks<M, false, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else if (refill_) simulate_walks<M, true, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else simulate_walks<M, false, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
             SR_HIP(hipGetLastError());
             if (o_.profile) SR_HIP(hipEventRecord(lease.c->event(ev + 1), stream));
             stats.expand_launches++;
@@ -334,7 +416,7 @@ class SimEngine final : public SimEngineBase {
             for (u32 i = 0; i < NSHARD; ++i) {
                 const SimShard& s = host[0].shard[i];
                 states += s.states;
-                for (int r = 1; r < 4; ++r) ended[r] += s.ended[r];
+                for (u32 r = 1; r < SIM_ENDS; ++r) ended[r] += s.ended[r];
                 longest = std::max(longest, s.longest);
             }
             started += n;
@@ -353,9 +435,9 @@ class SimEngine final : public SimEngineBase {
                 std::fprintf(stderr, "[sr] simulation batch %llu: walks %llu, states %llu, longest %u\n",
                              (unsigned long long)stats.levels, (unsigned long long)started, (unsigned long long)states, longest);
             if (ended[SIM_FAULT]) throw Error(SR_ERR_UNSUPPORTED, model_fault_text(m_));
-            if (ended[1] + ended[2] + ended[3] != started)
-                throw Error(SR_ERR_HIP, "simulation: a batch ended " + std::to_string(ended[1] + ended[2] + ended[3]) + " of " +
-                                            std::to_string(started) + " walks");
+            const u64 done = ended[SIM_TERMINAL] + ended[SIM_DEPTH] + ended[SIM_FAULT] + ended[SIM_LOOP];
+            if (done != started)
+                throw Error(SR_ERR_HIP, "simulation: a batch ended " + std::to_string(done) + " of " + std::to_string(started) + " walks");
             if (all) {
                 reference_done = true;
                 break;
@@ -379,15 +461,26 @@ class SimEngine final : public SimEngineBase {
         stats.total_sec = secs(t_start, Clock::now());
     }
 
-    // The discovery of property p: walk w of its hit (t, w), cut at step t, re-walked on the host.
+    // The discovery of property p: walk w of its hit (t, w), cut at step t, re-walked on the host. With
+    // loop detection the hit of an `eventually` property may be a lasso (the walk ended with SIM_LOOP
+    // at t): the walk was ended on equal FINGERPRINTS, so the path is returned only after its last
+    // state and the state at loop_start were compared word for word.
     SimHostWalk discovery_walk(int p) const {
         const u64 key = hits_[p];
         const u32 t = (u32)(key >> 40);
         const u64 w = key & (SIM_MAX_WALKS - 1);
-        SimHostWalk r = sim_host_walk(m_, o_.seed, w, o_.max_depth, true, t);
+        SimHostWalk r = sim_host_walk(m_, o_.seed, w, o_.max_depth, o_.loops != 0, true, t);
         if (r.steps < t || r.first_hit[p] != (int)t)
             throw Error(SR_ERR_NONDETERMINISM, "simulation: the host walk " + std::to_string(w) + " does not reproduce the device's hit of \"" +
                                                    std::string(m_.prop_name(p)) + "\" at step " + std::to_string(t));
+        if ((emask_ >> p & 1) && r.end == SIM_LOOP && r.steps == t) {
+            const u32 j = r.loop_start;
+            if (j >= t || r.words.size() != (size_t)(t + 1) * W ||
+                !std::equal(r.words.begin() + (size_t)j * W, r.words.begin() + (size_t)(j + 1) * W, r.words.begin() + (size_t)t * W))
+                throw Error(SR_ERR_NONDETERMINISM, "simulation: fingerprint collision: walk " + std::to_string(w) + " ended as a loop at step " +
+                                                       std::to_string(t) + ", but its state there differs from the state at step " +
+                                                       std::to_string(j) + "; no lasso is reported for \"" + std::string(m_.prop_name(p)) + "\"");
+        }
         return r;
     }
     int chain(int p, std::vector<u64>& out) override {
@@ -413,9 +506,14 @@ class SimEngine final : public SimEngineBase {
     i64 sim_records(u32* steps, u32* end, u64* fp, i64 cap) const override {
         for (i64 i = 0; i < std::min<i64>(cap, (i64)records_.size()); ++i) {
             if (steps) steps[i] = records_[i].steps;
-            if (end) end[i] = records_[i].end;
+            if (end) end[i] = records_[i].end & 0xff;
             if (fp) fp[i] = records_[i].fp;
         }
+        return (i64)records_.size();
+    }
+    i64 sim_loop_starts(u32* start, i64 cap) const override {
+        for (i64 i = 0; start && i < std::min<i64>(cap, (i64)records_.size()); ++i)
+            start[i] = (records_[i].end & 0xff) == SIM_LOOP ? records_[i].end >> 8 : SIM_NO_LOOP;
         return (i64)records_.size();
     }
 
