@@ -72,7 +72,7 @@ enum sr_model_id {
     SR_MODEL_SINGLE_COPY = 12,    /* (client_count<=6, server_count; <=8 actors) examples/single-copy-register.rs */
     SR_MODEL_LADDER = 13,         /* (rungs<=62, free_bits<=57) test fixture: rungs + free_bits action slots,
                                      (rungs + 1) * 2^free_bits states (stateright_amd/csrc/models.hpp Ladder) */
-    SR_MODEL_SPREAD = 14          /* (words: 1, 2 or 4; key_bits: free_bits < key_bits <= min(64 words, 128);
+    SR_MODEL_SPREAD = 14,         /* (words: 1, 2 or 4; key_bits: free_bits < key_bits <= min(64 words, 128);
                                      free_bits<=24; loops<=4; mark < 2^free_bits) test fixture: the subsets of
                                      free_bits bits packed into a pseudo-random key of key_bits bits, so the
                                      visited set's slot encoding is a parameter; 2^free_bits states, `loops`
@@ -80,6 +80,13 @@ enum sr_model_id {
                                      Optionally followed by (roots, dup): the init states are the subsets
                                      0 .. roots-1, then 0 .. dup-1 again; 1 <= roots <= 2^free_bits,
                                      dup <= roots, roots + dup <= 512 (default 1, 0) */
+    SR_MODEL_LIVE_GRAPH = 15      /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512[, words]) test fixture with
+                                     cycles: states v < 2^n_bits; r(v, k) = fmix64(fmix64(seed ^ v) + k) (murmur3's
+                                     finalizer); v has no actions iff t_mod > 0 and r(v, degree) % t_mod == 0, else
+                                     slot k < degree leads to r(v, k) mod 2^n_bits (action id k); one `eventually`
+                                     property "marked": p_mod > 0 and r(v, degree + 1) % p_mod == 0; init states
+                                     0 .. roots-1; words = 1 (default), 2 or 4 pads the state with words that are
+                                     functions of v (stateright_amd/csrc/models.hpp LiveGraph) */
 };
 
 /* Visit order inside a BFS level. */
@@ -123,6 +130,12 @@ typedef struct sr_opts {
                                     2pc, plugins with `canonical`): one state per orbit, order-
                                     independent counts; NOT the reference's DFS count, whose
                                     representatives are not canonical (src/checker/dfs.rs:258-283) */
+    int32_t reserved0;           /* what were 4 bytes of tail padding; never read                  */
+    int32_t liveness;            /* 1 = the complete `eventually` check (see sr_gpu_bfs_liveness below); 0 = off,
+                                    and then nothing changes. The struct grew from 56 to 64 bytes for it: a
+                                    caller whose struct_size is 56 is read as liveness = 0, whatever its
+                                    padding holds                                                   */
+    int32_t reserved1;
 } sr_opts;
 
 /* Timing/throughput counters of a finished run (sr_gpu_bfs_stats / sr_gpu_bfs_stats_sized).
@@ -261,6 +274,64 @@ int64_t sr_gpu_bfs_visits(const sr_bfs* bfs, int64_t* out, int64_t cap);
  * search gathers every rank's records at join, so its tree is global on every rank. */
 int64_t sr_gpu_bfs_visit_tree(const sr_bfs* bfs, int64_t* parent, int64_t* action, int64_t cap);
 void sr_gpu_bfs_free(sr_bfs* bfs);
+
+/* ---- The complete `eventually` check (sr_opts.liveness = 1; stateright_amd/csrc/live.hpp has the
+ * definition, for host and device from one source) ----
+ * The search refutes an `eventually` property only at a terminal state reached with the property's
+ * bit still set, and the bits are not part of the visited key, so it reports "holds" for a state
+ * that is reached first along a path on which the property held and later along one on which it did
+ * not, and for a path round a cycle on which it never holds (the reference's FIXMEs,
+ * src/checker/bfs.rs:239-256, pinned in src/checker.rs:400-413). With liveness = 1 a search that
+ * ended having explored everything is followed, per `eventually` property p still without a
+ * discovery, by a backward fixpoint over the reachable set: N_p = the reachable states where p's
+ * condition does not hold; F_p = the greatest subset of N_p in which every state is terminal (no
+ * action yields a next state within the boundary) or has a successor in F_p. p has a counterexample
+ * iff an init state is in F_p, and then the discovery of p is the deterministic witness: from the
+ * init state of lowest index in F_p, always through the lowest action slot whose next state is in
+ * F_p, to a terminal state (loop_start -1) or to the first state equal to an earlier one of the path
+ * (a lasso: the path's LAST state EQUALS its state at index loop_start; the two are compared word
+ * for word before the path is returned). sr_gpu_bfs_discovery / _discovery_path serve it like any
+ * other discovery. After the pass, no discovery of an `eventually` property means it holds on every
+ * maximal path. A property the search itself discovered keeps that discovery.
+ * Not covered: no fairness is assumed, so any self-loop on a state where p does not hold refutes p;
+ * the witness is not the shortest counterexample; one GPU and registered models only. Refused at
+ * spawn with SR_ERR_UNSUPPORTED: target_state_count (a partial set makes the fixpoint unsound), the
+ * partitioned spawns, symmetry, plugins, a capacity_hint beyond 2^32 - 1 states (a check that reaches
+ * more fails at the pass). A successor the visited set does not hold fails the check with
+ * SR_ERR_NONDETERMINISM. */
+typedef struct sr_live_result {
+    int32_t ran;            /* 1 = the pass ran for this property                                  */
+    int32_t init_index;     /* the init state (order of init_states) the witness starts at; -1 = no
+                               init state is in F_p: the property holds                            */
+    uint64_t not_p_states;  /* |N_p|                                                               */
+    uint64_t surviving;     /* |F_p|                                                               */
+    uint64_t examined;      /* worklist entries examined over all rounds                           */
+    uint32_t rounds;        /* rounds until one removed nothing (an implementation detail: states
+                               are removed in place, so it depends on the order; never compare it) */
+    uint32_t reserved0;
+    int64_t witness_len;    /* steps of the witness; -1 without one                                */
+    int64_t loop_start;     /* index of the path's state that its last state repeats; -1 = none, or
+                               the witness ends at a terminal state                                */
+    double pass_ms;         /* wall time of the pass for this property                             */
+} sr_live_result;
+/* The pass' outcome for property `prop` of a joined check (ran = 0: liveness off, not an `eventually`
+ * property, discovered by the search itself, or the search did not explore everything). */
+int32_t sr_gpu_bfs_liveness(const sr_bfs* bfs, int32_t prop, sr_live_result* out);
+/* Host-only (no device needed): a host search of a registered model over at most max_states states
+ * (SR_ERR_CAPACITY beyond), then the fixpoint and the witness for its `eventually` property `prop`.
+ * Writes the witness' canonical action ids (at most cap). Returns the model's unique state count,
+ * or a negative SR_ERR_*. */
+int64_t sr_liveness_host(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int64_t max_states,
+                         sr_live_result* out, int64_t* action_ids, int32_t cap);
+/* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
+ * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds
+ * them. The dump is int64s: [states, init states, properties, the init states' numbers..., then per
+ * state in number order: a bit mask of the properties whose CONDITION holds there, its successor
+ * count, and per successor within the boundary, in `actions()` order, (canonical action id, number)].
+ * Writes at most cap of them; returns the length of the whole dump, or a negative SR_ERR_*. What the
+ * tests of the complete `eventually` check run their own fixpoint over. */
+int64_t sr_host_graph(int32_t model_id, const int64_t* params, int32_t nparams, int64_t max_states, int64_t* out,
+                      int64_t cap);
 
 /* ---- Random-walk simulation checker (the counterpart of the simulation checker Stateright gained
  * after 0.28; stateright_amd/csrc/sim.hpp defines the walk, for host and device from one source) ----

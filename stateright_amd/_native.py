@@ -23,6 +23,7 @@ SR_MODEL_ABD = 11
 SR_MODEL_SINGLE_COPY = 12
 SR_MODEL_LADDER = 13
 SR_MODEL_SPREAD = 14
+SR_MODEL_LIVE_GRAPH = 15
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
@@ -43,7 +44,28 @@ class sr_opts(ctypes.Structure):
         ("counters", ctypes.c_int32),
         ("defer_paths", ctypes.c_int32),
         ("symmetry", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("liveness", ctypes.c_int32),  # (the struct grew from 56 to 64 bytes for it)
+        ("reserved1", ctypes.c_int32),
     ]
+
+
+class sr_live_result(ctypes.Structure):
+    _fields_ = [
+        ("ran", ctypes.c_int32),
+        ("init_index", ctypes.c_int32),
+        ("not_p_states", ctypes.c_uint64),
+        ("surviving", ctypes.c_uint64),
+        ("examined", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
+        ("witness_len", ctypes.c_int64),
+        ("loop_start", ctypes.c_int64),
+        ("pass_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved0"}
 
 
 class sr_sim_opts(ctypes.Structure):
@@ -173,6 +195,10 @@ SIGNATURES = [
     ("sr_gpu_bfs_visits", ctypes.c_int64, [_P, _I64P, ctypes.c_int64]),
     ("sr_gpu_bfs_visit_tree", ctypes.c_int64, [_P, _I64P, _I64P, ctypes.c_int64]),
     ("sr_gpu_bfs_free", None, [_P]),
+    ("sr_gpu_bfs_liveness", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(sr_live_result)]),
+    ("sr_host_graph", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int64, _I64P, ctypes.c_int64]),
+    ("sr_liveness_host", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                          ctypes.POINTER(sr_live_result), _I64P, ctypes.c_int32]),
     ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
     ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
     ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -316,6 +342,55 @@ def sim_walk(model_id, params, seed, walk, max_depth=4096, nprops=32, loops=Fals
            "attempts": att.value}
     if loops:
         out["loop_start"] = start.value
+    return out
+
+
+def host_graph(model_id, params, max_states=1 << 22):
+    """The reachable graph of a registered model by a host search (sr_host_graph; no device needed):
+    (succ, inits, conds) with succ[i] = [(canonical action id, j)] in `actions()` order, inits the init
+    states' numbers in order, and conds[i] the bit mask of the properties whose condition holds at i."""
+    import numpy as np
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    n = lib.sr_host_graph(model_id, arr, len(params), max_states, None, 0)
+    if n < 0:
+        raise ValueError(f"sr_host_graph: {last_error()} (status {n})")
+    buf = np.zeros(n, dtype=np.int64)
+    lib.sr_host_graph(model_id, arr, len(params), max_states, buf.ctypes.data_as(_I64P), n)
+    d = buf.tolist()
+    states, k = d[0], d[1]
+    inits, at = d[3:3 + k], 3 + k
+    succ, conds = [], []
+    for _ in range(states):
+        conds.append(d[at])
+        c = d[at + 1]
+        succ.append(list(zip(d[at + 2:at + 2 + 2 * c:2], d[at + 3:at + 3 + 2 * c:2])))
+        at += 2 + 2 * c
+    return succ, inits, conds
+
+
+def liveness_host(model_id, params, prop=0, max_states=1 << 22):
+    """The complete `eventually` check of a registered model on the host (csrc/live.hpp; no device
+    needed): a host search over at most `max_states` states, the fixpoint and the deterministic
+    witness for the `eventually` property of index `prop`. The dict of sr_live_result, plus `unique`
+    (the model's reachable states) and `actions` (the witness' canonical action ids; [] without one)."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    res = sr_live_result()
+    cap = 1 << 16
+    while True:
+        acts = (ctypes.c_int64 * cap)()
+        n = lib.sr_liveness_host(model_id, arr, len(params), prop, max_states, ctypes.byref(res), acts, cap)
+        if n < 0:
+            raise ValueError(f"sr_liveness_host: {last_error()} (status {n})")
+        if res.witness_len <= cap:
+            break
+        cap = res.witness_len
+    out = res.as_dict()
+    out["unique"] = n
+    out["actions"] = list(acts[:max(0, res.witness_len)])
     return out
 
 

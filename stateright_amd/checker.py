@@ -193,6 +193,21 @@ class CheckerBuilder:
         self._opts.profile = int(bool(on))
         return self
 
+    def complete_liveness(self, on=True):
+        """Engine opt-in: the complete `eventually` check. `spawn_bfs`, like the
+        reference, refutes an `eventually` property only at a terminal state reached with the
+        property's bit still set, so it misses a counterexample through a state that was first reached
+        on a path where the property held, and every counterexample that runs round a cycle
+        (src/checker.rs:400-413). With this on, a search that explored everything is followed by a
+        backward fixpoint over the reachable set on the GPU: a property without a discovery then holds
+        on every maximal path, and a discovery made by the pass is a terminal path or a lasso
+        (`GpuBfsChecker.loop_start`, `liveness`), which `assert_discovery` then accepts. No fairness is
+        assumed (a self-loop on a state where the property does not hold refutes it), the witness is
+        not the shortest one, and `target_state_count`, partitions / comm, `symmetry_canonical` and
+        plugin models are refused at spawn. Off by default; with it off nothing changes."""
+        self._opts.liveness = int(bool(on))
+        return self
+
     def verbose(self, on=True):
         self._opts.verbose = int(bool(on))
         return self
@@ -294,6 +309,8 @@ class CheckerBuilder:
 class GpuBfsChecker:
     """The `Checker` trait (src/checker.rs:184-338) implemented by the MI355X engine."""
 
+    PATH_BUFFER = 65536  # states the first buffers of discovery() / discovery_fingerprints() hold (they regrow)
+
     def __init__(self, model, opts, visitor=None, comm=None, partitions=1):
         lib = N.load()
         self._lib = lib
@@ -314,6 +331,7 @@ class GpuBfsChecker:
                                                        model.MODEL_ID, arr, len(params), ctypes.byref(opts))
         else:
             self._h = lib.sr_gpu_bfs_spawn(model.MODEL_ID, arr, len(params), ctypes.byref(opts))
+        self._liveness = bool(opts.liveness)
         self._spawned("sr_gpu_bfs_spawn")
 
     def _spawned(self, what):
@@ -395,23 +413,32 @@ class GpuBfsChecker:
     def discovery_fingerprints(self, name):
         """The fingerprint chain init..discovery (`reconstruct_path` input, bfs.rs:314-342)."""
         i = self._prop_index(name)
-        buf = (ctypes.c_uint64 * 65536)()
-        n = self._lib.sr_gpu_bfs_discovery(self._h, i, buf, 65536)
-        if n < 0:
-            raise CheckerError("sr_gpu_bfs_discovery", n)
-        return list(buf[:n])
+        cap = self.PATH_BUFFER
+        while True:  # (a witness of the liveness pass may be longer than the first buffer)
+            buf = (ctypes.c_uint64 * cap)()
+            n = self._lib.sr_gpu_bfs_discovery(self._h, i, buf, cap)
+            if n < 0:
+                raise CheckerError("sr_gpu_bfs_discovery", n)
+            if n <= cap:
+                return list(buf[:n])
+            cap = n
 
     def discovery(self, name):
         """`discovery` (src/checker.rs:211-213): the Path for `name`, or None."""
         i = self._prop_index(name)
-        acts = (ctypes.c_int64 * 65536)()
         width = self._lib.sr_gpu_bfs_describe_width(self._h)
-        states = (ctypes.c_int64 * (65536 * max(1, width)))()
-        n = self._lib.sr_gpu_bfs_discovery_path(self._h, i, acts, 65536, states, 65536 * max(1, width))
-        if n == -1:
-            return None
-        if n < 0:
-            raise CheckerError("sr_gpu_bfs_discovery_path", n)
+        cap = self.PATH_BUFFER
+        while True:  # (a witness of the liveness pass may be longer than the first buffers)
+            acts = (ctypes.c_int64 * cap)()
+            states = (ctypes.c_int64 * (cap * max(1, width)))()
+            n = self._lib.sr_gpu_bfs_discovery_path(self._h, i, acts, cap, states, cap * max(1, width))
+            if n == -1:
+                return None
+            if n < 0:
+                raise CheckerError("sr_gpu_bfs_discovery_path", n)
+            if n < cap:
+                break
+            cap = n + 1
         flat = list(states[:(n + 1) * width])
         st = [tuple(flat[k:k + width]) for k in range(0, len(flat), width)]
         ids = list(acts[:n])
@@ -490,6 +517,25 @@ class GpuBfsChecker:
         s = N.sr_stats()
         self._lib.sr_gpu_bfs_stats_sized(self._h, ctypes.byref(s), ctypes.sizeof(s))
         return s.as_dict()
+
+    def liveness(self, name):
+        """The complete `eventually` check's outcome for property `name` (`complete_liveness()`), a dict:
+        ran (0: the option is off, `name` is no `eventually` property, the search itself discovered it,
+        or the search did not explore everything), not_p_states (reachable states where the condition
+        does not hold), surviving (those from which a path exists on which it never holds), rounds (an
+        implementation detail), examined, witness_len (steps; -1 without a witness), loop_start (-1:
+        none, or a terminal witness), init_index (-1: the property holds) and pass_ms."""
+        r = N.sr_live_result()
+        st = self._lib.sr_gpu_bfs_liveness(self._h, self._prop_index(name), ctypes.byref(r))
+        if st != 0:
+            raise CheckerError("sr_gpu_bfs_liveness", st)
+        return r.as_dict()
+
+    def loop_start(self, name):
+        """`complete_liveness()`: if the discovery of the `eventually` property `name` is a lasso found
+        by the pass, the index of the path's state that its last state repeats; None otherwise."""
+        r = self.liveness(name)
+        return r["loop_start"] if r["ran"] and r["witness_len"] >= 0 and r["loop_start"] >= 0 else None
 
     def launch_profile(self):
         """profile(): [(kernel_ms, frontier)] of every expand launch, in launch order."""
@@ -579,13 +625,21 @@ class GpuBfsChecker:
         flat = list(conds)
         return [flat[k * n_props:(k + 1) * n_props] for k in range(len(ids) + 1)], bool(term.value)
 
+    def _accepts_lassos(self):
+        """Whether this check can report a lasso for an `eventually` property (`complete_liveness()`)."""
+        return self._liveness
+
     def assert_discovery(self, name, actions):
         """`assert_discovery` (src/checker.rs:292-337): the actions, from some init state, lead to a
         state violating an `always` / satisfying a `sometimes` property, or along a path on which
-        an `eventually` property never holds and that ends at a terminal state."""
+        an `eventually` property never holds and that ends at a terminal state. Only a check that can
+        report lassos (`complete_liveness()`; the simulation checker's `detect_loops=True`) also accepts,
+        for an `eventually` property, a path that ends at a state equal to an earlier state of the
+        path: the cycle between them can repeat forever."""
         found = self.assert_any_discovery(name)
         i = self._prop_index(name)
         exp = self.properties()[i][1]
+        loops = exp == Expectation.Eventually and self._accepts_lassos()
         info = []
         for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):
             r = self.replay_trace(actions, init)
@@ -599,12 +653,16 @@ class GpuBfsChecker:
                 return
             if exp == Expectation.Eventually:
                 satisfied = any(s[i] for s in per_state)
-                if not satisfied and terminal:
+                closed = False
+                if loops:
+                    states, _ = self.replay(actions, init)
+                    closed = states[-1] in states[:-1]
+                if not satisfied and (terminal or closed):
                     return
                 if satisfied:
                     info.append("incorrect counterexample satisfies eventually property")
-                if not terminal:
-                    info.append("incorrect counterexample is nonterminal")
+                if not (terminal or closed):
+                    info.append("incorrect counterexample is nonterminal" + (" and closes no loop" if loops else ""))
         extra = f" ({'; '.join(info)})" if info else ""
         raise AssertionError(f'Invalid discovery for "{name}"{extra}, but a valid one was found. '
                              f"found={found.into_actions()}")
@@ -695,29 +753,10 @@ class GpuSimulationChecker(GpuBfsChecker):
         w = self.host_walk(walk)
         return w["loop_start"] if w["end"] == N.SIM_LOOP and w["steps"] == step else None
 
-    def assert_discovery(self, name, actions):
-        """As the base class's, and with detect_loops=True an `eventually` property also accepts a
-        lasso: a path on which the property never holds and which ends at a terminal state OR at a
-        state equal to an earlier state of the path (the cycle between them can repeat forever)."""
-        i = self._prop_index(name)
-        if not self._sim_opts.loops or self.properties()[i][1] != Expectation.Eventually:
-            return super().assert_discovery(name, actions)
-        found = self.assert_any_discovery(name)
-        info = []
-        for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):
-            r = self.replay_trace(actions, init)
-            if r is None:
-                continue
-            per_state, terminal = r
-            states, _ = self.replay(actions, init)
-            closed = states[-1] in states[:-1]
-            satisfied = any(s[i] for s in per_state)
-            if not satisfied and (terminal or closed):
-                return
-            if satisfied:
-                info.append("incorrect counterexample satisfies eventually property")
-            if not (terminal or closed):
-                info.append("incorrect counterexample is nonterminal and closes no loop")
-        extra = f" ({'; '.join(info)})" if info else ""
-        raise AssertionError(f'Invalid discovery for "{name}"{extra}, but a valid one was found. '
-                             f"found={found.into_actions()}")
+    def _accepts_lassos(self):
+        """detect_loops=True: `assert_discovery` (the base class's) accepts a lasso for an `eventually`
+        property."""
+        return bool(self._sim_opts.loops)
+
+    def liveness(self, name):
+        raise NotImplementedError("liveness: the simulation checker keeps no reachable set (complete_liveness is spawn_bfs's)")

@@ -39,12 +39,23 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_ABD:
         case SR_MODEL_SINGLE_COPY:
             return reg_registers(a);
-        case SR_MODEL_SPREAD: return reg_spread(a);
+        case SR_MODEL_SPREAD:
+        case SR_MODEL_LIVE_GRAPH:
+            return reg_spread(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
 
+// The complete `eventually` check (sr_opts.liveness, live.hpp) runs on one GPU over a registered model.
+static void refuse_liveness(const sr_opts& o, bool partitioned, bool plugin) {
+    if (!o.liveness) return;
+    if (partitioned) throw Error(SR_ERR_UNSUPPORTED, "liveness with a partitioned search: the fixpoint runs on one GPU's visited set and arena");
+    if (plugin) throw Error(SR_ERR_UNSUPPORTED, "liveness with a plugin model: registered models only");
+    if (o.symmetry) throw Error(SR_ERR_UNSUPPORTED, "liveness with symmetry: the fixpoint runs on concrete states, not on orbit representatives");
+}
+
 static std::unique_ptr<EngineBase> make_engine(int model, const i64* p, int np, const sr_opts& o) {
+    refuse_liveness(o, false, false);
     return make_model_engine(EngineArgs{model, p, np, &o, false, nullptr, 0});
 }
 
@@ -325,6 +336,7 @@ static sr_bfs* spawn_plugin(const sr_plugin* pl, sr_dist* comm, int32_t vparts, 
             throw Error(SR_ERR_ARG, std::string("plugin ") + (pl->name ? pl->name : "?") + " was built against other headers (abi " +
                                         std::to_string(pl->abi) + ", engine " + std::to_string(SR_PLUGIN_ABI) + ")");
         sr_opts o = normalized_opts(opts);
+        refuse_liveness(o, comm != nullptr || vparts > 1, true);
         if (comm) o.device = comm->c->device;
         if (sr_device_count() <= 0) throw Error(SR_ERR_NO_DEVICE, "no HIP device visible");
         char err[512] = {0};
@@ -422,6 +434,8 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             return f(Ladder{(int)p[0], (int)p[1]});
         case SR_MODEL_SPREAD:
             return with_spread_model(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_LIVE_GRAPH:
+            return with_live_graph(p, np, [&](const auto& m) -> i64 { return f(m); });
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -579,6 +593,88 @@ int64_t sr_sim_walk_loops(int32_t model, const int64_t* p, int32_t np, uint64_t 
             return (i64)h.steps;
         });
         if (r == SR_ERR_UNSUPPORTED) set_error("sr_sim_walk: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int32_t sr_gpu_bfs_liveness(const sr_bfs* b, int32_t prop, sr_live_result* out) {
+    if (!b || !out || !b->e->finished.load(std::memory_order_acquire) || !b->e->live_result(prop, out)) return SR_ERR_ARG;
+    return SR_OK;
+}
+
+int64_t sr_liveness_host(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_live_result* out,
+                         int64_t* action_ids, int32_t cap) {
+    try {
+        if (!out || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host: out and max_states >= 1");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            if constexpr (has_emask<M>::value) {
+                const LiveHost h = live_host(m, prop, (u64)max_states);
+                *out = h.r;
+                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
+                return (i64)h.unique;
+            } else {
+                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
+            }
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int64_t sr_host_graph(int32_t model, const int64_t* p, int32_t np, int64_t max_states, int64_t* out, int64_t cap) {
+    try {
+        if (max_states < 1 || (cap > 0 && !out)) throw Error(SR_ERR_ARG, "sr_host_graph: max_states >= 1 and a buffer of cap");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            constexpr int W = M::W;
+            std::map<std::vector<u64>, i64> index;
+            std::vector<std::vector<u64>> st;
+            auto add = [&](const u64* s) {
+                std::vector<u64> v(s, s + W);
+                auto it = index.find(v);
+                if (it != index.end()) return it->second;
+                if ((i64)st.size() >= max_states)
+                    throw Error(SR_ERR_CAPACITY, "sr_host_graph: more than " + std::to_string(max_states) + " reachable states (max_states)");
+                index.emplace(v, (i64)st.size());
+                st.push_back(std::move(v));
+                return (i64)st.size() - 1;
+            };
+            std::vector<i64> dump{0, 0, M::NPROPS};
+            const std::vector<u64> inits = init_states_of(m);
+            for (size_t i = 0; i + W <= inits.size(); i += W) dump.push_back(add(&inits[i]));
+            dump[1] = (i64)dump.size() - 3;
+            for (size_t q = 0; q < st.size(); ++q) {
+                const std::vector<u64> s = st[q];  // (a copy: add() grows st)
+                i64 conds = 0;
+                for (int pr = 0; pr < M::NPROPS; ++pr)
+                    if ((m.expectation(pr) == ALWAYS) != m.discovers(pr, s.data())) conds |= (i64)1 << pr;
+                dump.push_back(conds);
+                const size_t at = dump.size();
+                dump.push_back(0);
+                for_each_successor(m, s.data(), [&](int a, const u64* ns) {
+                    dump.push_back(m.action_id(s.data(), a));
+                    dump.push_back(add(ns));
+                    dump[at] += 1;
+                });
+            }
+            dump[0] = (i64)st.size();
+            std::copy(dump.begin(), dump.begin() + (size_t)std::min<i64>(std::max<i64>(cap, 0), (i64)dump.size()), out);
+            return (i64)dump.size();
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_host_graph: model " + std::to_string(model) + " has no host form");
         return r;
     } catch (const Error& x) {
         set_error(x.what());
@@ -1242,6 +1338,7 @@ sr_bfs* sr_gpu_bfs_spawn_partitioned(sr_dist* comm, int32_t virtual_parts, int32
                                      int32_t nparams, const sr_opts* opts) {
     try {
         sr_opts o = normalized_opts(opts);
+        refuse_liveness(o, true, false);
         if (comm) o.device = comm->c->device;
         if (sr_device_count() <= 0) throw Error(SR_ERR_NO_DEVICE, "no HIP device visible");
         return start(make_model_engine(EngineArgs{model_id, params, nparams, &o, true, comm ? comm->c.get() : nullptr, (int)virtual_parts}));

@@ -24,6 +24,7 @@
 #include "../../include/stateright_gpu.h"
 #include "device.hpp"
 #include "kernels.hpp"
+#include "live.hpp"
 
 namespace sr {
 
@@ -73,7 +74,14 @@ class EngineBase {
                        std::vector<int>* all_conds = nullptr, int* terminal = nullptr) const = 0;
     virtual int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                         std::vector<i64>& states) const = 0;
+    // The complete `eventually` check's outcome for property p (live.hpp); false: p is no property.
+    virtual bool live_result(int p, sr_live_result* out) const {
+        if (p < 0 || p >= nprops()) return false;
+        *out = p < (int)live.size() ? live[p] : live_result_none();
+        return true;
+    }
 
+    std::vector<sr_live_result> live;  // per property (empty: the pass never ran)
     std::atomic<u64> state_count{0}, unique{0};
     std::atomic<u32> max_depth{0};
     std::atomic<bool> finished{false};
@@ -306,6 +314,14 @@ class Engine final : public EngineBase {
         : m_(m), o_(o), A_((u32)m.max_actions()), D_((u32)m.max_out_degree()), emask_(model_emask(m)) {
         disc.resize(M::NPROPS);
         (void)init_states_of(m_);  // a model with more init states than it declares fails at spawn
+        if (o_.liveness) {  // the complete `eventually` check (live.hpp): what it cannot be combined with
+            if (o_.target_state_count)
+                throw Error(SR_ERR_UNSUPPORTED, "liveness with target_state_count: a partial reachable set makes the fixpoint unsound");
+            if (is_canon<M>::value)
+                throw Error(SR_ERR_UNSUPPORTED, "liveness with symmetry: the fixpoint runs on concrete states, not on orbit representatives");
+            if (o_.capacity_hint > 0xffffffffull)
+                throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
+        }
         // Internal tuning knobs (not part of the ABI): successors per lane per probe round and
         // the visited-set load factor the capacity hint is sized for.
         if (const char* e = std::getenv("SR_PROBE_BATCH")) probe_batch_ = std::atoi(e);
@@ -396,6 +412,7 @@ class Engine final : public EngineBase {
     int chain(int p, std::vector<u64>& out) override {
         out.clear();
         if (p < 0 || p >= M::NPROPS || !disc[p].found) return 0;
+        if (!live_path_[p].empty()) return fingerprint_chain(m_, live_path_[p], out);  // (found by the liveness pass)
         SR_HIP(hipSetDevice(o_.device));
         std::vector<u64> st;
         tree_path(disc[p].level, disc[p].rank, st);
@@ -423,6 +440,7 @@ class Engine final : public EngineBase {
     // `Path::from_fingerprints` (src/checker/path.rs:20-86) on the host copy of the GpuModel.
     int path(int p, std::vector<i64>& actions, std::vector<i64>& states) override {
         if (p < 0 || p >= M::NPROPS || !disc[p].found) return -1;
+        if (!live_path_[p].empty()) return concrete_path(m_, live_path_[p], actions, states);
         SR_HIP(hipSetDevice(o_.device));
         std::vector<u64> st;
         tree_path(disc[p].level, disc[p].rank, st);
@@ -883,6 +901,8 @@ class Engine final : public EngineBase {
         unique = 0;
         max_depth = 0;
         for (auto& d : disc) d = DiscoveryRec{};
+        live.clear();
+        live_path_.assign(M::NPROPS, {});
         stats = sr_stats{};
         stats.words_per_state = W;
         stats.order_used = (u32)order;
@@ -968,6 +988,7 @@ class Engine final : public EngineBase {
         u64 n = (u64)k, popped_before = 0;
         u32 level = 0;
         bool order_dependent = false;
+        bool explored_all = false;  // every level was expanded whole and the last one produced nothing
         auto t_loop = Clock::now();
         if (pipelined) order_dependent = pipeline_levels(n, sq_level0);
         else for (;;) {
@@ -1089,6 +1110,7 @@ class Engine final : public EngineBase {
                 else if (stop) reference_done = true;     // all properties discovered
                 else  // exhausted: the last (partial) block still checks the target (bfs.rs:129-135)
                     reference_done = !(o_.target_state_count && state_count >= o_.target_state_count);
+                explored_all = !stop;
                 break;
             }
             lstart_.push_back(lstart_.back() + produced);
@@ -1101,6 +1123,7 @@ class Engine final : public EngineBase {
         stats.level_loop_sec = secs(t_loop, t_end);
         stats.total_sec = secs(t_start, t_end);
         stats.table_capacity = cap_;
+        if (o_.liveness && explored_all) live_pass();  // (reads the visited set: before its release)
         release_table();  // (the pipelined loop released it already)
         free_unzeroed_table();
         return order_dependent && !fifo_;
@@ -1299,6 +1322,141 @@ class Engine final : public EngineBase {
         SR_HIP(stream_sync(stream_));
         keys_.reset();
     }
+
+    // The complete `eventually` check (live.hpp, kernels_live.hpp) behind a search that explored
+    // everything: per `eventually` property still without a discovery, live_mark, then live_trim
+    // until a round removes nothing (one counter read-back per round, as for a level; the worklist
+    // shrinks, so later rounds are cheap), and if an init state survived, the witness by live_walk.
+    // The arena is R, the final visited set names its states. Every buffer lives for this call only.
+    void live_pass() {
+        live.assign(M::NPROPS, live_result_none());
+        if constexpr (has_emask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
+            u32 todo = 0;
+            for (int p = 0; p < M::NPROPS; ++p)
+                if ((emask_ >> p & 1) && !disc[p].found) todo |= 1u << p;
+            if (!todo) return;
+            if (lstart_.back() > 0xffffffffull)
+                throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
+            const u32 n = (u32)lstart_.back();
+            const TableView t = view();
+            const size_t bwords = (size_t)((cap_ + 31) / 32);
+            DBuf<u64> slot_of, lcb, out;
+            DBuf<u32> alive, onpath, wl[2];
+            slot_of.alloc(o_.device, n);
+            alive.alloc(o_.device, bwords);
+            wl[0].alloc(o_.device, n);
+            wl[1].alloc(o_.device, n);
+            lcb.alloc(o_.device, (sizeof(LiveCounters) + 7) / 8);
+            LiveCounters* lc = reinterpret_cast<LiveCounters*>(lcb.p);
+            LiveCounters h{};
+            auto read_back = [&] {  // the launch's counters (waits for it)
+                SR_HIP(hipGetLastError());
+                SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, stream_));
+                SR_HIP(stream_sync(stream_));
+                if (h.err & LIVE_ERR_LOOKUP)
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: find_slot did not find a reachable state, or a successor of one, in the "
+                                                       "visited set (an engine error: such a state is never taken as \"not alive\")");
+                if (h.err & LIVE_ERR_STUCK)
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: a state of the fixpoint has successors, none of them in the fixpoint");
+            };
+            const std::vector<u64> inits = init_states_of(m_);
+            const u32 k = (u32)(inits.size() / W);  // level 0 of the arena: the init states in REVERSE order
+            u32 walk_steps = LIVE_WALK_STEPS;
+            if (const char* e = std::getenv("SR_LIVE_WALK_STEPS"))  // (tests: several launches on a short witness)
+                if (std::atoi(e) > 0) walk_steps = std::min<u32>((u32)std::atoi(e), LIVE_WALK_STEPS);
+            for (; todo; todo &= todo - 1) {
+                const int p = __builtin_ctz(todo);
+                const auto t0 = Clock::now();
+                sr_live_result& r = live[p];
+                r.ran = 1;
+                SR_HIP(hipMemsetAsync(alive.p, 0, bwords * sizeof(u32), stream_));
+                SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
+                live_mark<M><<<blocks_for(n, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, n, t, p, slot_of.p, alive.p, wl[0].p, lc);
+                read_back();
+                u32 cnt = h.next_n;
+                r.not_p_states = r.surviving = cnt;
+                for (int cur = 0;; cur ^= 1) {  // (every round but the last removes a state)
+                    r.rounds += 1;
+                    r.examined += cnt;
+                    h.next_n = h.removed = 0;
+                    if (cnt) {
+                        SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
+                        live_trim<M><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of.p, alive.p, wl[cur].p,
+                                                                                             cnt, wl[cur ^ 1].p, lc);
+                        read_back();
+                    }
+                    r.surviving -= h.removed;
+                    cnt = h.next_n;
+                    if (o_.verbose)
+                        std::fprintf(stderr, "[sr] liveness \"%s\" round %u: removed %u, worklist %u, surviving %llu\n", m_.prop_name(p),
+                                     r.rounds, h.removed, cnt, (unsigned long long)r.surviving);
+                    if (!h.removed) break;
+                }
+                // the init state of lowest index whose bit survived (one launch, one read-back)
+                SR_HIP(hipMemsetAsync(&lc->first_init, 0xff, sizeof(u32), stream_));
+                live_first_init<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of.p, alive.p, k, lc);
+                read_back();
+                if (h.first_init < k) r.init_index = (int32_t)h.first_init;
+                if (r.init_index >= 0) {
+                    if (!onpath.p) onpath.alloc(o_.device, bwords);
+                    if (!out.p) out.alloc(o_.device, ((size_t)walk_steps + 1) * W);
+                    SR_HIP(hipMemsetAsync(onpath.p, 0, bwords * sizeof(u32), stream_));
+                    std::vector<u64> path(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
+                    SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
+                    for (u32 resume = 0;; resume = 1) {  // (each launch but the last takes walk_steps steps; |F_p| in all)
+                        SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
+                        live_walk<M><<<1, 64, 0, stream_>>>(m_, t, alive.p, onpath.p, out.p, walk_steps, resume, lc);
+                        read_back();
+                        if (h.steps > walk_steps) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
+                        const size_t o = path.size();
+                        path.resize(o + (size_t)h.steps * W);
+                        if (h.steps)
+                            SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)h.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
+                        if (path.size() / W - 1 > r.surviving)
+                            throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than the fixpoint has states");
+                        if (h.end != LIVE_WALK_MORE) break;
+                        if (!h.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
+                        SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)h.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+                    }
+                    live_accept(p, r, path, h.end == LIVE_WALK_LOOP);
+                }
+                r.pass_ms = secs(t0, Clock::now()) * 1e3;
+            }
+        }
+    }
+
+    // The device's witness is replayed on the host model before it becomes the discovery of p: every
+    // step is a successor in `actions()` order (concrete_path), the condition of p holds on no state,
+    // and the path ends at a terminal state or (lasso) at a state EQUAL, word for word, to an earlier
+    // one; the device ended the walk on equal visited-set slots, which in fingerprint mode are equal
+    // 64-bit fingerprints.
+    void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, bool lasso) {
+        const size_t len = path.size() / W - 1;
+        const std::string name = m_.prop_name(p);
+        std::vector<i64> acts, described;
+        concrete_path(m_, path, acts, described);
+        for (size_t i = 0; i <= len; ++i)
+            if (!live_not_p(m_, p, &path[i * W]))
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
+        const u64* last = &path[len * W];
+        if (lasso) {
+            size_t j = 0;
+            while (j < len && !std::equal(last, last + W, &path[j * W])) ++j;
+            if (j == len)
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: fingerprint collision: the witness of \"" + name + "\" ended as a loop at step " +
+                                                       std::to_string(len) + ", but its state there equals no earlier state of the path");
+            r.loop_start = (int64_t)j;
+        } else {
+            bool any = false;
+            for_each_successor(m_, last, [&](int, const u64*) { any = true; });
+            if (any) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness of \"" + name + "\" ends at a state that is not terminal");
+        }
+        r.witness_len = (int64_t)len;
+        live_path_[p] = path;
+        disc[p].found = true;
+        disc[p].level = disc[p].rank = 0;
+    }
+    std::vector<std::vector<u64>> live_path_;  // per property: the states of a discovery made by the liveness pass
 
     // Launch of the level whose frontier (n states) ends the arena, after the previous one is done:
     // the visited set and the arena are grown first if the level might not fit.

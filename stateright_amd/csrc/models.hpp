@@ -951,4 +951,61 @@ struct IncrementLock {
     }
 };
 
+// -----------------------------------------------------------------------------------------------
+// LiveGraph(n_bits, degree, seed, p_mod, t_mod, roots): a test fixture (no reference counterpart)
+// with cycles at scale, for the complete `eventually` check (live.hpp): a pseudo-random graph of
+// out-degree `degree` over the states v < 2^n_bits (n_bits <= 24, degree 1..4), one word, whose
+// packed key is v itself, so every quotient encoding applies. The key is DECLARED n_bits + 8 bits
+// wide: most of the 2^n_bits states are reachable, and a table with at least as many slots as the
+// key space has values homes every key in its first half (kernels.hpp make_table_view: a 1-bit
+// remainder), where a dense key space would pile into probe runs of millions of slots; the 8 spare
+// bits keep the hashed keys sparse, as Spread's filler does. With r(v, k) = fmix64((fmix64(seed ^ v) + k) mod 2^64):
+//   v has no actions iff t_mod > 0 and r(v, degree) % t_mod == 0 (a terminal state);
+//   otherwise slot k < degree leads to r(v, k) mod 2^n_bits; the action id is k.
+// eventually "marked": p_mod > 0 and r(v, degree + 1) % p_mod == 0. Init states 0 .. roots-1
+// (1 <= roots <= 512). An optional seventh parameter, words = 1 (the default), 2 or 4, widens the state:
+// word i >= 1 holds fmix64(v + an odd constant of i), so every word is loaded, stored, shuffled and
+// compared (equal v <=> equal words), while the graph, the key and the description stay those of v.
+// -----------------------------------------------------------------------------------------------
+template <int W_>
+struct LiveGraphT {
+    static_assert(W_ == 1 || W_ == 2 || W_ == 4, "LiveGraph: 1, 2 or 4 words");
+    static constexpr int W = W_, MW = 1, NPROPS = 1;
+    int n_bits, degree;
+    u64 seed;
+    u32 p_mod, t_mod;
+    int roots;
+    SR_HD u64 r(u64 v, u64 k) const { return fmix64(fmix64(seed ^ v) + k); }
+    int max_actions() const { return degree; }
+    int max_out_degree() const { return degree; }
+    u32 emask() const { return 1u; }
+    SR_HD void enabled(const u64* s, u64* m) const { m[0] = t_mod && r(s[0], (u64)degree) % t_mod == 0 ? 0ull : (1ull << degree) - 1; }
+    SR_HD static void pack(u64 v, u64* o) {
+        o[0] = v;
+#pragma unroll
+        for (int i = 1; i < W_; ++i) o[i] = fmix64(v + 0x9E3779B97F4A7C15ull * (u64)(2 * i + 1));
+    }
+    SR_HD bool apply(const u64* s, int a, u64* o) const {
+        pack(r(s[0], (u64)a) & ((1ull << n_bits) - 1), o);
+        return true;
+    }
+    SR_HD bool discovers(int, const u64* s) const { return p_mod && r(s[0], (u64)degree + 1) % p_mod == 0; }  // the condition holds
+    int init_count() const { return roots; }
+    int init_states(u64* out) const {
+        for (int i = 0; i < roots; ++i) pack((u64)i, out + i * W_);
+        return roots;
+    }
+    int expectation(int) const { return EVENTUALLY; }
+    const char* prop_name(int) const { return "marked"; }
+    int qkey_bits() const { return n_bits + 8; }
+    SR_HD unsigned __int128 qkey(const u64* s) const { return s[0]; }
+    int describe_width() const { return 1; }
+    void describe(const u64* s, i64* d) const { d[0] = (i64)s[0]; }
+    void undescribe(const i64* d, u64* s) const { pack((u64)d[0] & ((1ull << n_bits) - 1), s); }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return degree; }
+    std::string action_name(i64 id) const { return "Edge(" + std::to_string(id) + ")"; }
+};
+using LiveGraph = LiveGraphT<1>;
+
 }  // namespace sr

@@ -53,7 +53,25 @@ std::unique_ptr<EngineBase> reg_paxos_wide(const EngineArgs& a);      // paxos, 
 std::unique_ptr<EngineBase> reg_ping_pong(const EngineArgs& a);       // ping-pong
 std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 slots) and the single-copy register
 std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
-std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4)
+std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4), LiveGraph
+
+// The LiveGraph fixture (models.hpp) of (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words
+// (default 1), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip)
+// validate alike.
+template <class F>
+auto with_live_graph(const i64* p, int np, F&& f) {
+    if (np != 6 && np != 7) throw Error(SR_ERR_ARG, "live graph needs 6 params (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words");
+    if (p[0] < 1 || p[0] > 24) throw Error(SR_ERR_UNSUPPORTED, "live graph: n_bits must be in 1..=24");
+    if (p[1] < 1 || p[1] > 4) throw Error(SR_ERR_UNSUPPORTED, "live graph: degree must be in 1..=4");
+    if (p[3] < 0 || p[3] > 0xffffffffll || p[4] < 0 || p[4] > 0xffffffffll)
+        throw Error(SR_ERR_ARG, "live graph: p_mod and t_mod must be in 0..2^32-1");
+    if (p[5] < 1 || p[5] > 512 || p[5] > (i64)1 << p[0]) throw Error(SR_ERR_ARG, "live graph: roots must be in 1..=min(512, 2^n_bits)");
+    const i64 w = np > 6 ? p[6] : 1;
+    if (w != 1 && w != 2 && w != 4) throw Error(SR_ERR_UNSUPPORTED, "live graph: words must be 1, 2 or 4");
+    if (w == 1) return f(LiveGraphT<1>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
+    if (w == 2) return f(LiveGraphT<2>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
+    return f(LiveGraphT<4>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
+}
 
 // The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark) and
 // optionally (roots, dup), its init states (default 1, 0), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip) validate alike.

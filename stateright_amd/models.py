@@ -211,6 +211,23 @@ class Spread(_Model):
         return p if (self.roots, self.dup) == (1, 0) else p + [self.roots, self.dup]
 
 
+class LiveGraph(_Model):
+    """Test fixture without a reference counterpart (csrc/models.hpp `LiveGraph`): a pseudo-random
+    graph with cycles over the states v < 2**n_bits, out-degree `degree` (1..4), for the complete
+    `eventually` check. r(v, k) = fmix64((fmix64(seed ^ v) + k) mod 2**64); v is terminal iff t_mod > 0
+    and r(v, degree) % t_mod == 0, else slot k leads to r(v, k) mod 2**n_bits; `eventually "marked"`
+    holds at v iff p_mod > 0 and r(v, degree + 1) % p_mod == 0; the init states are 0 .. roots-1."""
+    MODEL_ID = N.SR_MODEL_LIVE_GRAPH
+
+    def __init__(self, n_bits, degree, seed, p_mod, t_mod=0, roots=1, words=1):
+        self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots = n_bits, degree, seed, p_mod, t_mod, roots
+        self.words = words  # 2 or 4: the same graph on states padded with words that are functions of v
+
+    def params(self):
+        p = [self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots]
+        return p if self.words == 1 else p + [self.words]
+
+
 class SingleCopyRegister(_Model):
     """The single-copy register `SingleCopyModelCfg { client_count, server_count }.into_model()`
     (examples/single-copy-register.rs:40-78): SingleCopyActor servers (a register value each, no
