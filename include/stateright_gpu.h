@@ -366,8 +366,33 @@ int64_t sr_host_graph(int32_t model_id, const int64_t* params, int32_t nparams, 
  * trace, but a path is returned only after the two states were compared in full; a collision fails
  * the call with SR_ERR_NONDETERMINISM and a message that says so).
  *
+ * Distinct-state count (sr_sim_opts.unique = 1; off by default, and with it off nothing changes: no
+ * kernel, count, record, hit or allocation). For a check that ran the traces 0 .. n-1,
+ *   U = { fingerprint(s_t) : 0 <= w < n, 0 <= t <= steps(w) }:
+ * every state a trace visits, its init state and its last state included, exactly the states
+ * state_count counts. Every visit inserts the state's 64-bit fingerprint into a table in device
+ * memory that all traces share and that lives across the batches of the check; unique_state_count is
+ * then |U|, sr_gpu_sim_unique_fingerprints returns U and sr_gpu_sim_batch_new how many fingerprints
+ * each batch added. The mode feeds nothing back: trace w, its record, its hits and the check's stop
+ * point are the same with it on or off. U is a union, so |U|, the set and the per-batch counts are
+ * functions of (model, seed, traces run, max_depth, loops, batch size) and of nothing else (not of
+ * the kernel's form, the grid or the order of launches). Fingerprints are compared, not states:
+ * exact for models whose state is one packed word (their fingerprint is a bijection), a 64-bit hash
+ * for wider states, where n distinct states lose one to a collision with probability ~n^2 / 2^65.
+ * What it is: a measure of how much ground the traces covered and of whether more traces still
+ * reach anything new (the per-batch counts decay as coverage saturates). What it is not: a proof.
+ * States no trace reached are not in it, |U| below the reachable count says nothing about the rest,
+ * and a run stopped by stale_batches has still proved nothing: sr_gpu_bfs_is_done keeps meaning
+ * "every property discovered". The table has the smallest power of two >= 2 * unique_capacity slots
+ * of 8 bytes (open addressing, at most min(slots, 1024) probes per insert). An insert whose probes
+ * run out is dropped and sets `overflow`: |U| is then a lower bound (with at most 1024 slots the
+ * table is then full and |U| equals its slots). Without an overflow the count and the set are
+ * exact up to fingerprint collisions. The table is allocated when the check starts and released
+ * when it ends; U leaves the device compacted, |U| * 8 bytes of host memory.
+ *
  * Every sr_gpu_bfs_* accessor works on the handle. unique_state_count is SET EQUAL to state_count
- * (states visited, repeats included: there is no visited set), max_depth is the longest trace in
+ * (states visited, repeats included: there is no visited set) unless sr_sim_opts.unique is set (then
+ * it is |U| above), max_depth is the longest trace in
  * steps, sr_stats.levels the number of batches, expand_launches the launches and successors =
  * state_count - traces started; visits are empty and the visit tree is unsupported. Registered
  * models only (no plugins, no partitions, no symmetry reduction). */
@@ -384,10 +409,48 @@ typedef struct sr_sim_opts {
     int32_t verbose;             /* one log line per batch on stderr                             */
     int32_t profile;             /* time every launch with HIP events                            */
     int32_t loops;               /* 1 = loop detection (end reason 4, lasso discoveries); 0 = off */
+    int32_t reserved0;           /* the tail padding of the 56-byte struct: never read            */
+    /* (the struct grew from 56 to 72 bytes here: a caller whose struct_size is 56 is read as all
+     * three below being zero, whatever its padding holds)                                         */
+    int32_t unique;              /* 1 = count distinct states (see above); 0 = off               */
+    uint32_t stale_batches;      /* k > 0: also stop after the first whole batch that ends a run of k
+                                    consecutive batches with no new fingerprint; needs unique = 1
+                                    (SR_ERR_ARG otherwise) and counts as a bound: walks = 0 without a
+                                    target_state_count is then accepted. An overflow of the table
+                                    fails such a check with SR_ERR_CAPACITY                       */
+    uint64_t unique_capacity;    /* distinct fingerprints the table is sized for (slots: the smallest
+                                    power of two >= twice that); 0 = min(walks * (max_depth + 1),
+                                    2^28), or 2^28 when walks is 0                                */
 } sr_sim_opts;
 /* Zeroes the caller's mirror of `size` bytes (at most the library's own size) and sets struct_size
  * to what it wrote and max_depth to 4096. */
 void sr_sim_opts_init_sized(sr_sim_opts* opts, uint32_t size);
+/* The distinct-state count of a simulation (sr_sim_opts.unique). */
+typedef struct sr_sim_unique_result {
+    uint32_t struct_size;   /* sizeof this struct in the caller's build (set before the call)     */
+    int32_t on;             /* the mode was on; with 0 every field below but batches is 0          */
+    uint64_t unique;        /* |U|: distinct fingerprints in the table (a lower bound if overflow) */
+    int32_t overflow;       /* an insert was dropped: its probe limit ran out                      */
+    int32_t stopped_stale;  /* the check stopped by stale_batches                                  */
+    uint64_t slots;         /* the table's slots                                                   */
+    uint64_t capacity;      /* the capacity the table was sized for                                */
+    uint64_t batches;       /* batches run                                                         */
+} sr_sim_unique_result;
+/* Fills *out (at most out->struct_size bytes) for a finished simulation. SR_ERR_ARG for a handle
+ * that is no simulation or still runs. */
+int32_t sr_gpu_sim_unique(const sr_bfs* sim, sr_sim_unique_result* out);
+/* The fingerprints of U, sorted ascending (sorted once, at the first call). Writes at most cap of
+ * them; returns |U| as counted in the table, or a negative SR_ERR_* (SR_ERR_ARG: no simulation, still
+ * running, or the mode was off). */
+int64_t sr_gpu_sim_unique_fingerprints(sr_bfs* sim, uint64_t* out, int64_t cap);
+/* Per batch, in order, the number of fingerprints it added to U; their sum is |U|. Returns the
+ * number of batches (at most cap are written); 0 with the mode off (nothing is recorded then). */
+int64_t sr_gpu_sim_batch_new(const sr_bfs* sim, uint64_t* out, int64_t cap);
+/* Host-only (no device needed): U of the traces walk0 .. walk0 + nwalks - 1 of a registered model,
+ * by the same definition. Writes the distinct fingerprints sorted ascending (at most cap); returns
+ * their number, or a negative SR_ERR_*. */
+int64_t sr_sim_unique_host(int32_t model_id, const int64_t* params, int32_t nparams, uint64_t seed, uint64_t walk0,
+                           uint64_t nwalks, uint32_t max_depth, int32_t loops, uint64_t* out, int64_t cap);
 /* Spawns the simulation; returns NULL on error (see sr_last_error). Non-blocking. */
 sr_bfs* sr_gpu_sim_spawn(int32_t model_id, const int64_t* params, int32_t nparams, const sr_sim_opts* opts);
 /* record_walks = 1: per trace, by trace index, its steps, end reason (1 terminal, 2 depth, 3 fault,

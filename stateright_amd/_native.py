@@ -80,7 +80,27 @@ class sr_sim_opts(ctypes.Structure):
         ("verbose", ctypes.c_int32),
         ("profile", ctypes.c_int32),
         ("loops", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),  # (the tail padding of the 56-byte struct: never read)
+        ("unique", ctypes.c_int32),  # (the struct grew from 56 to 72 bytes for the distinct-state count)
+        ("stale_batches", ctypes.c_uint32),
+        ("unique_capacity", ctypes.c_uint64),
     ]
+
+
+class sr_sim_unique_result(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("on", ctypes.c_int32),
+        ("unique", ctypes.c_uint64),
+        ("overflow", ctypes.c_int32),
+        ("stopped_stale", ctypes.c_int32),
+        ("slots", ctypes.c_uint64),
+        ("capacity", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
 # end reasons of a simulated walk (csrc/sim.hpp SimEnd); SIM_LOOP only with loop detection
@@ -212,6 +232,12 @@ SIGNATURES = [
                                            ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("sr_gpu_sim_unique", ctypes.c_int32, [_P, ctypes.POINTER(sr_sim_unique_result)]),
+    ("sr_gpu_sim_unique_fingerprints", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]),
+    ("sr_gpu_sim_batch_new", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]),
+    ("sr_sim_unique_host", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.c_int64]),
     ("sr_dist_unique_id", ctypes.c_int32, [ctypes.c_char_p]),
     ("sr_dist_init", _P, [ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     ("sr_dist_local_group", ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
@@ -343,6 +369,24 @@ def sim_walk(model_id, params, seed, walk, max_depth=4096, nprops=32, loops=Fals
     if loops:
         out["loop_start"] = start.value
     return out
+
+
+def sim_unique_host(model_id, params, seed, walk0, nwalks, max_depth=4096, loops=False):
+    """The distinct-state set of the simulation checker on the host (sr_sim_unique_host, csrc/sim.hpp;
+    no device needed): the sorted distinct fingerprints of every state the walks walk0 .. walk0 +
+    nwalks - 1 visit, as a numpy uint64 array; what `spawn_simulation(count_unique=True)` collects on
+    the device."""
+    import numpy as np
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    n = lib.sr_sim_unique_host(model_id, arr, len(params), seed, walk0, nwalks, max_depth, int(bool(loops)), None, 0)
+    if n < 0:
+        raise ValueError(f"sr_sim_unique_host: {last_error()} (status {n})")
+    out = np.zeros(max(1, n), dtype=np.uint64)
+    lib.sr_sim_unique_host(model_id, arr, len(params), seed, walk0, nwalks, max_depth, int(bool(loops)),
+                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n)
+    return out[:n]
 
 
 def host_graph(model_id, params, max_states=1 << 22):

@@ -243,7 +243,8 @@ class CheckerBuilder:
         self._opts.order = N.SR_ORDER_FAST
         return self.spawn_bfs()
 
-    def spawn_simulation(self, seed, walks=None, max_depth=4096, record_walks=False, detect_loops=False):
+    def spawn_simulation(self, seed, walks=None, max_depth=4096, record_walks=False, detect_loops=False,
+                         count_unique=False, unique_capacity=None, until_stale=None):
         """The simulation checker (Stateright's `spawn_simulation`, added after the 0.28 mirrored here):
         `walks` independent random traces of at most `max_depth` steps from the init states, one GPU
         lane per trace, the properties evaluated on every state. No visited set is kept, so a model
@@ -257,10 +258,21 @@ class CheckerBuilder:
         checkpoint taken at a power-of-two step; the discovery's path ends at the state it repeats
         (`GpuSimulationChecker.loop_start`). No fairness is assumed.
 
+        count_unique=True (off by default; with it off nothing changes) also collects the fingerprints
+        of every state the traces visit in a table on the GPU: `unique_state_count()` is then the number
+        of DISTINCT states visited (`unique_fingerprints()`, `batch_new_states()`, `unique_info()`), a
+        measure of how much ground the traces covered and whether more of them still reach anything
+        new. It is a coverage measure, not a proof: states no trace reached are simply not in it. The
+        traces, records, hits and the stop point are the same with it on or off. The table is sized
+        for `unique_capacity` distinct states (default min(walks * (max_depth + 1), 2**28)); past it
+        the count is a lower bound (`unique_info()["overflow"]`). until_stale=k also stops the check
+        after the first whole batch that ends k consecutive batches without a new state; it needs
+        count_unique, stands in for `walks` as the check's bound, and an overflow then fails the check.
+
         Trace w is a pure function of (model, seed, w, max_depth, detect_loops) (csrc/sim.hpp), and the check stops
         after the first whole batch of traces at whose end every property is discovered,
         `target_state_count` is reached or `walks` traces have run. walks=None needs a
-        `target_state_count` (a property may never be discovered). Honours `device`,
+        `target_state_count` or `until_stale` (a property may never be discovered). Honours `device`,
         `target_state_count`, `verbose` and `profile`; a visitor, partitions / comm,
         `symmetry_canonical` and plugin models are refused. Non-blocking; call `join()`."""
         if self._visitor is not None:
@@ -273,7 +285,13 @@ class CheckerBuilder:
             raise ValueError("spawn_simulation: plugin models are not simulated (registered models only)")
         if not 1 <= int(max_depth) <= 2**20:
             raise ValueError("spawn_simulation: max_depth must be in 1..=2**20")
-        if walks is None and not self._opts.target_state_count:
+        if until_stale is not None and int(until_stale) < 1:
+            raise ValueError("spawn_simulation: until_stale must be positive")
+        if until_stale is not None and not count_unique:
+            raise ValueError("spawn_simulation: until_stale needs count_unique=True (it counts batches without a new distinct state)")
+        if unique_capacity is not None and not 1 <= int(unique_capacity) <= 2**30:
+            raise ValueError("spawn_simulation: unique_capacity must be in 1..=2**30")
+        if walks is None and not self._opts.target_state_count and until_stale is None:
             raise ValueError("spawn_simulation: give walks or a target_state_count (a property may never be discovered)")
         so = N.sr_sim_opts()
         N.load().sr_sim_opts_init_sized(ctypes.byref(so), ctypes.sizeof(so))
@@ -286,6 +304,9 @@ class CheckerBuilder:
         so.verbose = self._opts.verbose
         so.profile = self._opts.profile
         so.loops = int(bool(detect_loops))
+        so.unique = int(bool(count_unique))
+        so.stale_batches = 0 if until_stale is None else int(until_stale)
+        so.unique_capacity = 0 if unique_capacity is None else int(unique_capacity)
         if walks is not None and so.walks == 0:
             raise ValueError("spawn_simulation: walks must be positive")
         return GpuSimulationChecker(self._model, so)
@@ -672,9 +693,12 @@ class GpuSimulationChecker(GpuBfsChecker):
     """The `Checker` trait over the simulation checker (`CheckerBuilder.spawn_simulation`). `report`,
     `assert_*`, `discoveries`, `discovery` and `replay` are inherited unchanged, with these meanings:
     `state_count` is the number of states the walks visited, `unique_state_count` EQUALS it (there is
-    no visited set: repeats count), `max_depth` is the longest walk in steps, and `is_done` means
-    "every property discovered", so `assert_no_discovery` / `assert_properties` of a property that is
-    never violated report that model checking is incomplete: a run without a discovery proves nothing.
+    no visited set: repeats count) unless the check ran with `count_unique=True` (then it is the
+    number of distinct states visited, a lower bound if `unique_info()["overflow"]`; see
+    `unique_info`, `unique_fingerprints`, `batch_new_states`), `max_depth` is the longest walk in
+    steps, and `is_done` means "every property discovered", so `assert_no_discovery` /
+    `assert_properties` of a property that is never violated report that model checking is
+    incomplete: a run without a discovery proves nothing.
     With `detect_loops=True` the discovery of an `eventually` property may be a lasso (`loop_start`),
     which `assert_discovery` then accepts."""
 
@@ -757,6 +781,42 @@ class GpuSimulationChecker(GpuBfsChecker):
         """detect_loops=True: `assert_discovery` (the base class's) accepts a lasso for an `eventually`
         property."""
         return bool(self._sim_opts.loops)
+
+    def unique_info(self):
+        """The distinct-state count of a joined check: dict(on, unique, overflow (an insert was dropped:
+        `unique` is a lower bound), stopped_stale (the check stopped by until_stale), slots, capacity
+        (the table's geometry), batches). With count_unique off every entry but `batches` is 0."""
+        self.join()
+        res = N.sr_sim_unique_result()
+        res.struct_size = ctypes.sizeof(res)
+        st = self._lib.sr_gpu_sim_unique(self._h, ctypes.byref(res))
+        if st != 0:
+            raise CheckerError("sr_gpu_sim_unique", st)
+        return res.as_dict()
+
+    def unique_fingerprints(self):
+        """count_unique=True: the fingerprints of the distinct states visited, sorted ascending, as a
+        numpy uint64 array (compare with `_native.sim_unique_host`, or with `model_fingerprint` of
+        the states another checker visited)."""
+        import numpy as np
+        self.join()
+        n = self._lib.sr_gpu_sim_unique_fingerprints(self._h, None, 0)
+        if n < 0:
+            raise CheckerError("sr_gpu_sim_unique_fingerprints", n)
+        out = np.zeros(max(1, n), dtype=np.uint64)
+        self._lib.sr_gpu_sim_unique_fingerprints(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n)
+        return out[:n]
+
+    def batch_new_states(self):
+        """count_unique=True: per batch, in order, how many distinct states it added (their sum is
+        `unique_state_count()`): how coverage grew, and whether it still does. [] with the mode off."""
+        self.join()
+        n = self._lib.sr_gpu_sim_batch_new(self._h, None, 0)
+        if n < 0:
+            raise CheckerError("sr_gpu_sim_batch_new", n)
+        out = (ctypes.c_uint64 * max(1, n))()
+        self._lib.sr_gpu_sim_batch_new(self._h, out, n)
+        return list(out[:n])
 
     def liveness(self, name):
         raise NotImplementedError("liveness: the simulation checker keeps no reachable set (complete_liveness is spawn_bfs's)")

@@ -568,6 +568,63 @@ int32_t sr_gpu_sim_hit(const sr_bfs* b, int32_t prop, uint64_t* walk, uint32_t* 
     return e && e->sim_hit(prop, walk, step) ? 1 : 0;
 }
 
+int32_t sr_gpu_sim_unique(const sr_bfs* b, sr_sim_unique_result* out) {
+    const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
+    if (!e || !out || out->struct_size < sizeof(uint32_t) || !b->e->finished.load(std::memory_order_acquire)) {
+        set_error("sr_gpu_sim_unique: a finished simulation handle and a sized result");
+        return SR_ERR_ARG;
+    }
+    sr_sim_unique_result r = e->sim_unique();
+    if (!r.on) r.batches = e->stats.levels;
+    r.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(r));
+    std::memcpy(out, &r, r.struct_size);  // only the caller's own bytes
+    return SR_OK;
+}
+
+int64_t sr_gpu_sim_unique_fingerprints(sr_bfs* b, uint64_t* out, int64_t cap) {
+    SimEngineBase* e = b ? dynamic_cast<SimEngineBase*>(b->e.get()) : nullptr;
+    if (!e || !b->e->finished.load(std::memory_order_acquire)) {
+        set_error("sr_gpu_sim_unique_fingerprints: not a finished simulation handle");
+        return SR_ERR_ARG;
+    }
+    const int64_t n = e->sim_unique_fps(out, std::max<int64_t>(cap, 0));
+    if (n < 0) {
+        set_error("sr_gpu_sim_unique_fingerprints: the simulation ran without sr_sim_opts.unique");
+        return SR_ERR_ARG;
+    }
+    return n;
+}
+
+int64_t sr_gpu_sim_batch_new(const sr_bfs* b, uint64_t* out, int64_t cap) {
+    const SimEngineBase* e = b ? dynamic_cast<const SimEngineBase*>(b->e.get()) : nullptr;
+    if (!e || !b->e->finished.load(std::memory_order_acquire)) {
+        set_error("sr_gpu_sim_batch_new: not a finished simulation handle");
+        return SR_ERR_ARG;
+    }
+    return e->sim_batch_new(out, std::max<int64_t>(cap, 0));
+}
+
+int64_t sr_sim_unique_host(int32_t model, const int64_t* p, int32_t np, uint64_t seed, uint64_t walk0, uint64_t nwalks,
+                           uint32_t max_depth, int32_t loops, uint64_t* out, int64_t cap) {
+    try {
+        if (!max_depth || max_depth > SIM_MAX_DEPTH) throw Error(SR_ERR_ARG, "simulation: max_depth must be in 1..=2^20");
+        if (walk0 >= SIM_MAX_WALKS || nwalks > SIM_MAX_WALKS - walk0) throw Error(SR_ERR_ARG, "simulation: walks must be below 2^40");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            const std::vector<u64> fps = sim_unique_host(m, seed, walk0, nwalks, max_depth, loops != 0);
+            for (int64_t i = 0; out && i < cap && i < (int64_t)fps.size(); ++i) out[i] = fps[(size_t)i];
+            return (i64)fps.size();
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_sim_unique_host: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
 int64_t sr_sim_walk(int32_t model, const int64_t* p, int32_t np, uint64_t seed, uint64_t walk, uint32_t max_depth,
                     int64_t* action_ids, int32_t cap, int32_t* end_reason, uint64_t* final_fp, int32_t* first_hit_step,
                     int32_t nprops, int32_t* attempts) {

@@ -68,8 +68,34 @@
 // reached target_state_count, or the walks are exhausted; so a check is a deterministic function of
 // (model, seed, walks, max_depth, batch size). Per property the hit with the smallest (t, w) is
 // kept: the shortest trace, ties to the lowest walk index. There is no visited set, so
-// `unique` is SET EQUAL to state_count (every visited state counts, repeats included), `max_depth`
-// is the longest walk in steps, and `is_done` means "every property discovered".
+// `unique` is SET EQUAL to state_count (every visited state counts, repeats included) unless the
+// distinct-state count below is on, `max_depth` is the longest walk in steps, and `is_done` means
+// "every property discovered".
+//
+// Distinct-state count (opt-in: sr_sim_opts.unique, `spawn_simulation(count_unique=True)`; with it
+// off no kernel, count, record, hit or allocation changes). For a check that ran the walks 0 .. n-1:
+//   U = { state_fp<M>(s_t) : 0 <= w < n, 0 <= t <= steps(w) }
+// Every state a walk visits is in U, its init state and its last state included, whatever the end
+// reason: exactly the states state_count counts (with loops on, the states of the cut walk). The
+// mode feeds nothing back into the walk: walk w, its record, its hits and the check's stop point
+// are bit-identical with the mode on or off (the stop rule `stale_batches`, which exists only with
+// the mode on, aside). U is a union, so it does not depend on lane, wave, launch order or the form
+// of the kernel, and |U|, the set and the number of new fingerprints per batch are deterministic
+// functions of (model, seed, walks run, max_depth, loops, batch size). Fingerprints are compared,
+// not states: exact for one-word states (state_fp is a bijection there), a 64-bit hash for wider
+// ones, so n distinct states lose one to a collision with probability ~n^2 / 2^65.
+// The host form is sim_unique_host below (sim_host_walk's fingerprints, sorted, distinct); the
+// device form inserts into a table in HBM while it walks (kernels_sim.hpp "Distinct-state table").
+// The table (both sides agree on it; only the device keeps one): `slots` 8-byte slots, a power of
+// two >= 2, 0 = vacant as in the BFS fingerprint table (kernels.hpp: state_fp is never 0, a one-word
+// fingerprint by construction, a wider one by the remap of 0 to 1 in fingerprint<W>, so no state
+// is mistaken for a vacant slot; the two wide states that hash to 0 and 1 count as one, which is
+// the collision above). Home slot sim_unique_home(f), linear probing, at most
+// sim_unique_probe_limit(slots) = min(slots, 1024) probes; an insert that exhausts them is dropped
+// and raises the overflow flag: |U| is then a lower bound (the host says so: unique_overflow).
+// A slot goes vacant -> fingerprint exactly once and nothing is ever removed, so while |U| <= slots
+// <= 1024 no insert is dropped (a probe sequence covers the whole table), and an overflow there
+// means the table is full: the count equals slots.
 #pragma once
 #include "engine.hpp"
 
@@ -82,6 +108,24 @@ constexpr u32 SIM_K_INIT = 0xFFFFFFFFu;
 constexpr u32 SIM_MAX_DEPTH = 1u << 20;
 constexpr u64 SIM_MAX_WALKS = 1ull << 40;
 constexpr u64 SIM_NO_HIT = ~0ull;
+constexpr u64 SIM_UNIQUE_MAX_CAPACITY = 1ull << 28;  // the default capacity's cap: 2^29 slots, 4 GiB
+constexpr u32 SIM_UNIQUE_MAX_PROBES = 1024;
+constexpr u64 SIM_UNIQUE_MAX_REQUEST = 1ull << 30;  // the largest unique_capacity accepted: 2^31 slots, 16 GiB
+constexpr u32 SIM_UNIQUE_TAIL = 16;  // words behind the slots: the overflow flag, the gather's cursor
+
+// The distinct-state table's geometry ("Distinct-state count" above).
+// Slots for a capacity of c fingerprints: the smallest power of two >= 2 c (load <= 0.5).
+SR_HD u64 sim_unique_slots(u64 c) {
+    u64 s = 2;
+    while (s < 2 * c) s <<= 1;
+    return s;
+}
+SR_HD u32 sim_unique_log2(u64 slots) { return (u32)__builtin_ctzll(slots); }
+SR_HD u32 sim_unique_probe_limit(u64 slots) { return (u32)(slots < SIM_UNIQUE_MAX_PROBES ? slots : SIM_UNIQUE_MAX_PROBES); }
+// Home slot: the top log2(slots) bits of the fingerprint times 2^64 / phi (a mix of all its bits; a
+// one-word fingerprint is fmix64 of a small integer, whose low bits alone are as good, but nothing
+// here relies on that).
+SR_HD u64 sim_unique_home(u64 f, u32 log2_slots) { return (f * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots); }
 
 SR_HD u64 sim_walk_key(u64 seed, u64 w) { return fmix64(seed + 0x9E3779B97F4A7C15ull * (w + 1)); }
 SR_HD u64 sim_rand_keyed(u64 key, u32 t, u32 k) { return fmix64((key ^ ((u64)t << 32 | k)) + 0x632BE59BD9B4E019ull); }
@@ -152,12 +196,23 @@ struct SimNoLoops {  // loop detection off: sim_advance compiles to the plain wa
     static constexpr bool on = false;
 };
 
+// state_fp<M>(s_t) for sim_advance's loop memory: computed there (SimFpOwn), or handed in by a caller
+// that has it already (SimFpGiven: the kernel's distinct-state insert), so that it is computed once.
+struct SimFpOwn {
+    static constexpr bool given = false;
+};
+struct SimFpGiven {
+    static constexpr bool given = true;
+    u64 f;
+};
+
 // Visits s_t and takes one step. emask: the model's `eventually` properties (the others are reported
 // where discovers() holds). on_hit(p, t) is called for every hit of the walk; on_step(s_t, a)
 // before the walk moves on through slot a. lp: SimLoops<Ring> or SimNoLoops.
 // Returns SIM_RUNNING (wk now holds s_{t+1}) or the reason the walk ended at s_t.
-template <class M, class Hit, class Step, class Loops>
-SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step, Loops& lp) {
+template <class M, class Hit, class Step, class Loops, class Fp = SimFpOwn>
+SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step, Loops& lp,
+                      const Fp& fpv = Fp{}) {
 #pragma unroll
     for (int p = 0; p < M::NPROPS; ++p) {
         if (emask >> p & 1) {
@@ -171,7 +226,9 @@ SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&
         if (m.faulted(wk.s)) return SIM_FAULT;
     }
     if constexpr (Loops::on) {
-        const u64 f = state_fp<M>(wk.s);
+        u64 f;
+        if constexpr (Fp::given) f = fpv.f;
+        else f = state_fp<M>(wk.s);
         const u32 t = wk.t;
         u32 j = t && lp.cf == f ? lp.ct : SIM_NO_LOOP;
         // the window, oldest first, so that the largest index wins (no early exit: every read is
@@ -281,7 +338,31 @@ class SimEngineBase : public EngineBase {
     virtual bool sim_hit(int p, u64* walk, u32* step) const = 0;
     virtual i64 sim_records(u32* steps, u32* end, u64* fp, i64 cap) const = 0;
     virtual i64 sim_loop_starts(u32* start, i64 cap) const = 0;
+    virtual const sr_sim_unique_result& sim_unique() const = 0;
+    virtual i64 sim_unique_fps(u64* out, i64 cap) = 0;  // -1: the mode was off
+    virtual i64 sim_batch_new(u64* out, i64 cap) const = 0;
 };
+
+// U of the walks [w0, w0 + n) on the host ("Distinct-state count" above): sorted, distinct.
+template <class M>
+std::vector<u64> sim_unique_host(const M& m, u64 seed, u64 w0, u64 n, u32 max_depth, bool loops) {
+    std::vector<u64> out;
+    auto settle = [&] {
+        std::sort(out.begin(), out.end());
+        out.erase(std::unique(out.begin(), out.end()), out.end());
+    };
+    size_t settled = 0;
+    for (u64 w = w0; w < w0 + n; ++w) {
+        const SimHostWalk h = sim_host_walk(m, seed, w, max_depth, loops, true);
+        out.insert(out.end(), h.fps.begin(), h.fps.end());
+        if (out.size() > 2 * settled + (1u << 20)) {  // (memory stays within a factor of the set)
+            settle();
+            settled = out.size();
+        }
+    }
+    settle();
+    return out;
+}
 
 // SR_SIM_REFILL: 1 = the persistent form (a lane whose walk ended takes the next unstarted index of
 // the batch), 0 = one walk per lane. Both give the same per-walk records and hits. The default is
@@ -376,6 +457,29 @@ class SimEngine final : public SimEngineBase {
         SR_HIP(hipDeviceGetAttribute(&ndev, hipDeviceAttributeMultiprocessorCount, o_.device));
         if (ndev <= 0) ndev = 256;
 
+        // distinct-state table: sized here, cleared once, shared by every batch, released below
+        DBuf<u64> uq;
+        uq_ = sr_sim_unique_result{};
+        uq_.struct_size = sizeof(uq_);
+        uq_fps_.clear();
+        uq_sorted_ = false;
+        batch_new_.clear();
+        u64 fresh = 0, stale_run = 0;
+        if (o_.unique) {
+            uq_.on = 1;
+            uq_.capacity = o_.unique_capacity ? o_.unique_capacity
+                           : total            ? std::min<u64>(total * ((u64)o_.max_depth + 1), SIM_UNIQUE_MAX_CAPACITY)
+                                              : SIM_UNIQUE_MAX_CAPACITY;
+            uq_.slots = sim_unique_slots(uq_.capacity);
+            uq.alloc(o_.device, (size_t)uq_.slots + SIM_UNIQUE_TAIL);  // the flag and the gather's cursor ride behind the slots
+            SR_HIP(hipMemsetAsync(uq.p, 0, ((size_t)uq_.slots + SIM_UNIQUE_TAIL) * sizeof(u64), stream));
+            a.uq_keys = uq.p;
+            a.uq_flag = reinterpret_cast<u32*>(uq.p + uq_.slots);
+            a.uq_log2 = sim_unique_log2(uq_.slots);
+            a.uq_limit = sim_unique_probe_limit(uq_.slots);
+            stats.table_capacity = uq_.slots;
+        }
+
         u64 states = 0, started = 0, ended[SIM_ENDS] = {};
         u32 longest = 0;
         const auto t_loop = Clock::now();
@@ -394,7 +498,12 @@ class SimEngine final : public SimEngineBase {
             if (refill_) grid = std::min<u32>(grid, grid_cap_ ? grid_cap_ : (u32)ndev * SIM_PERSIST_WAVES / (SIM_BLOCK / 64));
             const size_t ev = 2 * stats.expand_launches;
             if (o_.profile) SR_HIP(hipEventRecord(lease.c->event(ev), stream));
-            if (o_.loops && refill_) simulate_walks<M, true, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            // (the counting forms are compiled once per LOOPS: the persistent form's code, which with
+            // uq_refill = 0 reserves nothing and so is the static form)
+            a.uq_refill = refill_;
+            if (o_.unique && o_.loops) simulate_walks<M, true, true, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else if (o_.unique) simulate_walks<M, true, false, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
+            else if (o_.loops && refill_) simulate_walks<M, true, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
             else if (o_.loops) simulate_walks<M, false, true><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
             else if (refill_) simulate_walks<M, true, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
             else simulate_walks<M, false, false><<<grid, SIM_BLOCK, 0, stream>>>(m_, a, inl);
@@ -410,12 +519,16 @@ class SimEngine final : public SimEngineBase {
                 records_.resize(o + n);
                 SR_HIP(hipMemcpyAsync(&records_[o], rec.p, (size_t)n * sizeof(SimRecord), hipMemcpyDeviceToHost, stream));
             }
+            u32 uq_full = 0;
+            if (o_.unique) SR_HIP(hipMemcpyAsync(&uq_full, a.uq_flag, sizeof(u32), hipMemcpyDeviceToHost, stream));
             // the next batch starts from zeroed shards and cursor (the best hits carry over)
             SR_HIP(hipMemsetAsync(sd, 0, offsetof(SimDevice, best), stream));
             SR_HIP(stream_sync(stream));
+            u64 batch_fresh = 0;
             for (u32 i = 0; i < NSHARD; ++i) {
                 const SimShard& s = host[0].shard[i];
                 states += s.states;
+                batch_fresh += s.fresh;
                 for (u32 r = 1; r < SIM_ENDS; ++r) ended[r] += s.ended[r];
                 longest = std::max(longest, s.longest);
             }
@@ -429,7 +542,17 @@ class SimEngine final : public SimEngineBase {
                 all = all && disc[p].found;
             }
             state_count = states;
-            unique = states;  // no visited set: every visited state counts
+            if (o_.unique) {
+                fresh += batch_fresh;
+                batch_new_.push_back(batch_fresh);
+                stale_run = batch_fresh ? 0 : stale_run + 1;
+                uq_.unique = fresh;
+                uq_.overflow = uq_full != 0;
+                uq_.batches = stats.levels;
+                unique = fresh;  // |U| (a lower bound after an overflow)
+            } else {
+                unique = states;  // no visited set: every visited state counts
+            }
             max_depth = longest;
             if (o_.verbose)
                 std::fprintf(stderr, "[sr] simulation batch %llu: walks %llu, states %llu, longest %u\n",
@@ -438,15 +561,39 @@ class SimEngine final : public SimEngineBase {
             const u64 done = ended[SIM_TERMINAL] + ended[SIM_DEPTH] + ended[SIM_FAULT] + ended[SIM_LOOP];
             if (done != started)
                 throw Error(SR_ERR_HIP, "simulation: a batch ended " + std::to_string(done) + " of " + std::to_string(started) + " walks");
+            if (o_.stale_batches && uq_.overflow)
+                throw Error(SR_ERR_CAPACITY, "simulation: the distinct-state table of " + std::to_string(uq_.slots) +
+                                                 " slots overflowed under stale_batches (a full table takes no new fingerprint and would "
+                                                 "look stale forever); raise unique_capacity");
             if (all) {
                 reference_done = true;
                 break;
             }
             if (o_.target_state_count && states >= o_.target_state_count) break;
+            if (o_.stale_batches && stale_run >= o_.stale_batches) {
+                uq_.stopped_stale = 1;
+                break;
+            }
             if (b0 >= SIM_MAX_WALKS) break;
         }
         stats.successors = states - started;
         stats.level_loop_sec = secs(t_loop, Clock::now());
+        if (o_.unique && fresh) {  // the set leaves the device compacted; the table is released with this scope
+            DBuf<u64> out;
+            out.alloc(o_.device, (size_t)fresh);
+            unsigned long long* cursor = reinterpret_cast<unsigned long long*>(uq.p + uq_.slots + 1);
+            const u32 grid = (u32)std::min<u64>(blocks_for(uq_.slots, SIM_BLOCK), (u64)ndev * 8);
+            sim_unique_gather<<<grid, SIM_BLOCK, 0, stream>>>(uq.p, uq_.slots, out.p, fresh, cursor);
+            SR_HIP(hipGetLastError());
+            uq_fps_.resize((size_t)fresh);
+            u64 gathered = 0;
+            SR_HIP(hipMemcpyAsync(uq_fps_.data(), out.p, (size_t)fresh * sizeof(u64), hipMemcpyDeviceToHost, stream));
+            SR_HIP(hipMemcpyAsync(&gathered, cursor, sizeof(u64), hipMemcpyDeviceToHost, stream));
+            SR_HIP(stream_sync(stream));
+            if (gathered != fresh)
+                throw Error(SR_ERR_HIP, "simulation: the distinct-state table holds " + std::to_string(gathered) + " fingerprints, but " +
+                                            std::to_string(fresh) + " were counted");
+        }
         if (o_.profile && stats.expand_launches) {
             double ms = 0;
             launch_ms.assign(stats.expand_launches, 0.0);
@@ -516,6 +663,20 @@ class SimEngine final : public SimEngineBase {
             start[i] = (records_[i].end & 0xff) == SIM_LOOP ? records_[i].end >> 8 : SIM_NO_LOOP;
         return (i64)records_.size();
     }
+    const sr_sim_unique_result& sim_unique() const override { return uq_; }
+    i64 sim_unique_fps(u64* out, i64 cap) override {
+        if (!uq_.on) return -1;
+        if (!uq_sorted_) {  // once, on demand
+            std::sort(uq_fps_.begin(), uq_fps_.end());
+            uq_sorted_ = true;
+        }
+        for (i64 i = 0; out && i < std::min<i64>(cap, (i64)uq_fps_.size()); ++i) out[i] = uq_fps_[i];
+        return (i64)uq_fps_.size();
+    }
+    i64 sim_batch_new(u64* out, i64 cap) const override {
+        for (i64 i = 0; out && i < std::min<i64>(cap, (i64)batch_new_.size()); ++i) out[i] = batch_new_[i];
+        return (i64)batch_new_.size();
+    }
 
   private:
     M m_;
@@ -527,6 +688,10 @@ class SimEngine final : public SimEngineBase {
     std::vector<u64> inits_;
     std::vector<u64> hits_;          // per property: sim_hit_key of the best hit, SIM_NO_HIT = none
     std::vector<SimRecord> records_; // record_walks: one per walk started, by walk index
+    sr_sim_unique_result uq_{};      // distinct-state count: what sr_gpu_sim_unique reports
+    std::vector<u64> uq_fps_;        //   U as gathered from the table (sorted at the first request)
+    bool uq_sorted_ = false;
+    std::vector<u64> batch_new_;     //   per batch: the fingerprints it added
 };
 
 // Validated copy of a caller's sr_sim_opts (a shorter mirror is zero-extended, then defaulted).
@@ -538,7 +703,11 @@ inline sr_sim_opts normalized_sim_opts(const sr_sim_opts* opts) {
     if (!o.max_depth) o.max_depth = 4096;
     if (o.max_depth > SIM_MAX_DEPTH) throw Error(SR_ERR_ARG, "simulation: max_depth must be in 1..=2^20");
     if (o.walks >= SIM_MAX_WALKS) throw Error(SR_ERR_ARG, "simulation: walks must be below 2^40");
-    if (!o.walks && !o.target_state_count)
+    o.reserved0 = 0;  // (a 56-byte caller's tail padding: never read)
+    if (o.stale_batches && !o.unique)
+        throw Error(SR_ERR_ARG, "simulation: stale_batches needs unique = 1 (it counts batches without a new distinct state)");
+    if (o.unique_capacity > SIM_UNIQUE_MAX_REQUEST) throw Error(SR_ERR_ARG, "simulation: unique_capacity must be at most 2^30");
+    if (!o.walks && !o.target_state_count && !o.stale_batches)
         throw Error(SR_ERR_ARG, "simulation: walks or target_state_count must be set (a property may never be discovered)");
     return o;
 }
