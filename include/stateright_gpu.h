@@ -80,13 +80,19 @@ enum sr_model_id {
                                      Optionally followed by (roots, dup): the init states are the subsets
                                      0 .. roots-1, then 0 .. dup-1 again; 1 <= roots <= 2^free_bits,
                                      dup <= roots, roots + dup <= 512 (default 1, 0) */
-    SR_MODEL_LIVE_GRAPH = 15      /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512[, words]) test fixture with
+    SR_MODEL_LIVE_GRAPH = 15,     /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512[, words]) test fixture with
                                      cycles: states v < 2^n_bits; r(v, k) = fmix64(fmix64(seed ^ v) + k) (murmur3's
                                      finalizer); v has no actions iff t_mod > 0 and r(v, degree) % t_mod == 0, else
                                      slot k < degree leads to r(v, k) mod 2^n_bits (action id k); one `eventually`
                                      property "marked": p_mod > 0 and r(v, degree + 1) % p_mod == 0; init states
                                      0 .. roots-1; words = 1 (default), 2 or 4 pads the state with words that are
                                      functions of v (stateright_amd/csrc/models.hpp LiveGraph) */
+    SR_MODEL_2PC_LIVE = 16        /* (rm_count<=14) SR_MODEL_2PC (same states, action slots and counts) with two
+                                     `eventually` properties after its three: 3 "every RM decides" (every rm is
+                                     Committed or Aborted), 4 "every RM commits". No reference counterpart: 2pc
+                                     has no terminal state (once Commit or Abort is sent, RmRcvCommitMsg /
+                                     RmRcvAbortMsg stay enabled as self-loops), so it is the model of the complete
+                                     `eventually` check's progress mode (SR_LIVENESS_PROGRESS) */
 };
 
 /* Visit order inside a BFS level. */
@@ -95,6 +101,16 @@ enum sr_order {
     SR_ORDER_FIFO = 1, /* exactly the single-threaded reference order (pop_back/push_front)   */
     SR_ORDER_FAST = 2  /* any order inside a level: wave-aggregated append, no ordering pass  */
 };
+
+/* sr_opts.liveness: the complete `eventually` check (see sr_gpu_bfs_liveness below). Every value but 0
+ * and SR_LIVENESS_PROGRESS is read as SR_LIVENESS_COMPLETE. */
+enum sr_liveness_mode {
+    SR_LIVENESS_OFF = 0,
+    SR_LIVENESS_COMPLETE = 1, /* no fairness: a self-loop on a state where the property does not hold refutes it */
+    SR_LIVENESS_PROGRESS = 2  /* progress fairness: a successor equal to its state is no successor */
+};
+/* sr_live_result.end_kind: how the witness ends (both modes). */
+enum sr_live_end { SR_LIVE_END_NONE = 0, SR_LIVE_END_TERMINAL = 1, SR_LIVE_END_LOOP = 2, SR_LIVE_END_STUTTER = 3 };
 
 enum sr_expectation { SR_ALWAYS = 0, SR_EVENTUALLY = 1, SR_SOMETIMES = 2 }; /* src/lib.rs:293-300 */
 
@@ -131,7 +147,8 @@ typedef struct sr_opts {
                                     independent counts; NOT the reference's DFS count, whose
                                     representatives are not canonical (src/checker/dfs.rs:258-283) */
     int32_t reserved0;           /* what were 4 bytes of tail padding; never read                  */
-    int32_t liveness;            /* 1 = the complete `eventually` check (see sr_gpu_bfs_liveness below); 0 = off,
+    int32_t liveness;            /* 1 = the complete `eventually` check (see sr_gpu_bfs_liveness below); 2 = the
+                                    same under progress fairness (enum sr_liveness_mode); 0 = off,
                                     and then nothing changes. The struct grew from 56 to 64 bytes for it: a
                                     caller whose struct_size is 56 is read as liveness = 0, whatever its
                                     padding holds                                                   */
@@ -298,7 +315,18 @@ void sr_gpu_bfs_free(sr_bfs* bfs);
  * spawn with SR_ERR_UNSUPPORTED: target_state_count (a partial set makes the fixpoint unsound), the
  * partitioned spawns, symmetry, plugins, a capacity_hint beyond 2^32 - 1 states (a check that reaches
  * more fails at the pass). A successor the visited set does not hold fails the check with
- * SR_ERR_NONDETERMINISM. */
+ * SR_ERR_NONDETERMINISM.
+ * PROGRESS FAIRNESS (liveness = SR_LIVENESS_PROGRESS = 2, off by default): the same rule over
+ * succ'(s) = succ(s) \ {s}: a successor whose words all equal those of s is no successor, and a state
+ * is a sink if it is terminal or a STUTTER END (it has successors and every one is the state
+ * itself). F_p' is the greatest subset of N_p in which every state is such a sink or has a successor
+ * other than itself in F_p'; the witness steps over succ' only and ends at a terminal state, at a
+ * stutter end (end_kind 3, loop_start -1) or at the first repeated state, so a closed loop has at
+ * least two distinct states. No discovery then means: the property holds on every maximal path that
+ * does not stay forever in one state that has a successor other than itself. This is NOT per-action
+ * weak fairness: a cycle through two or more distinct states still refutes the property, and that is
+ * not repaired here. The refusals above apply unchanged; the simulation checker's loop detection
+ * (sr_sim_opts.loops) is not affected: there a self-loop still closes a lasso. */
 typedef struct sr_live_result {
     int32_t ran;            /* 1 = the pass ran for this property                                  */
     int32_t init_index;     /* the init state (order of init_states) the witness starts at; -1 = no
@@ -308,7 +336,9 @@ typedef struct sr_live_result {
     uint64_t examined;      /* worklist entries examined over all rounds                           */
     uint32_t rounds;        /* rounds until one removed nothing (an implementation detail: states
                                are removed in place, so it depends on the order; never compare it) */
-    uint32_t reserved0;
+    uint32_t end_kind;      /* enum sr_live_end: 0 no witness, 1 it ends at a terminal state, 2 it closes a
+                               loop, 3 (progress fairness only) it ends at a stutter end. What was
+                               `reserved0`: the size and every offset are unchanged                 */
     int64_t witness_len;    /* steps of the witness; -1 without one                                */
     int64_t loop_start;     /* index of the path's state that its last state repeats; -1 = none, or
                                the witness ends at a terminal state                                */
@@ -323,6 +353,14 @@ int32_t sr_gpu_bfs_liveness(const sr_bfs* bfs, int32_t prop, sr_live_result* out
  * or a negative SR_ERR_*. */
 int64_t sr_liveness_host(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int64_t max_states,
                          sr_live_result* out, int64_t* action_ids, int32_t cap);
+/* The same with the mode as an argument: fairness 0 = none (sr_liveness_host is this call), 1 = progress
+ * fairness (SR_ERR_ARG for any other value). */
+int64_t sr_liveness_host_fair(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int32_t fairness,
+                              int64_t max_states, sr_live_result* out, int64_t* action_ids, int32_t cap);
+/* Host-only: the sink kind of the state reached by the canonical action ids from init state `init` of
+ * a joined check's model: -1 the actions cannot be replayed, 0 the state has a successor other than
+ * itself, 1 it is terminal, 3 it is a stutter end (what `assert_discovery` asks in the progress mode). */
+int32_t sr_gpu_bfs_sink_kind(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n);
 /* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
  * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds
  * them. The dump is int64s: [states, init states, properties, the init states' numbers..., then per

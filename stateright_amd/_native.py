@@ -24,6 +24,7 @@ SR_MODEL_SINGLE_COPY = 12
 SR_MODEL_LADDER = 13
 SR_MODEL_SPREAD = 14
 SR_MODEL_LIVE_GRAPH = 15
+SR_MODEL_2PC_LIVE = 16
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
@@ -50,6 +51,11 @@ class sr_opts(ctypes.Structure):
     ]
 
 
+# sr_opts.liveness (enum sr_liveness_mode) and sr_live_result.end_kind (enum sr_live_end)
+SR_LIVENESS_OFF, SR_LIVENESS_COMPLETE, SR_LIVENESS_PROGRESS = 0, 1, 2
+SR_LIVE_END_NONE, SR_LIVE_END_TERMINAL, SR_LIVE_END_LOOP, SR_LIVE_END_STUTTER = 0, 1, 2, 3
+
+
 class sr_live_result(ctypes.Structure):
     _fields_ = [
         ("ran", ctypes.c_int32),
@@ -58,14 +64,14 @@ class sr_live_result(ctypes.Structure):
         ("surviving", ctypes.c_uint64),
         ("examined", ctypes.c_uint64),
         ("rounds", ctypes.c_uint32),
-        ("reserved0", ctypes.c_uint32),
+        ("end_kind", ctypes.c_uint32),  # (what was reserved0: same offset)
         ("witness_len", ctypes.c_int64),
         ("loop_start", ctypes.c_int64),
         ("pass_ms", ctypes.c_double),
     ]
 
     def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved0"}
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class sr_sim_opts(ctypes.Structure):
@@ -219,6 +225,9 @@ SIGNATURES = [
     ("sr_host_graph", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int64, _I64P, ctypes.c_int64]),
     ("sr_liveness_host", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                           ctypes.POINTER(sr_live_result), _I64P, ctypes.c_int32]),
+    ("sr_liveness_host_fair", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.POINTER(sr_live_result), _I64P, ctypes.c_int32]),
+    ("sr_gpu_bfs_sink_kind", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32]),
     ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
     ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
     ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -414,11 +423,12 @@ def host_graph(model_id, params, max_states=1 << 22):
     return succ, inits, conds
 
 
-def liveness_host(model_id, params, prop=0, max_states=1 << 22):
+def liveness_host(model_id, params, prop=0, max_states=1 << 22, fairness=0):
     """The complete `eventually` check of a registered model on the host (csrc/live.hpp; no device
     needed): a host search over at most `max_states` states, the fixpoint and the deterministic
     witness for the `eventually` property of index `prop`. The dict of sr_live_result, plus `unique`
-    (the model's reachable states) and `actions` (the witness' canonical action ids; [] without one)."""
+    (the model's reachable states) and `actions` (the witness' canonical action ids; [] without one).
+    fairness: 0 none, 1 progress fairness (a successor equal to its state is no successor)."""
     lib = load()
     params = list(params)
     arr = (ctypes.c_int64 * max(1, len(params)))(*params)
@@ -426,7 +436,7 @@ def liveness_host(model_id, params, prop=0, max_states=1 << 22):
     cap = 1 << 16
     while True:
         acts = (ctypes.c_int64 * cap)()
-        n = lib.sr_liveness_host(model_id, arr, len(params), prop, max_states, ctypes.byref(res), acts, cap)
+        n = lib.sr_liveness_host_fair(model_id, arr, len(params), prop, fairness, max_states, ctypes.byref(res), acts, cap)
         if n < 0:
             raise ValueError(f"sr_liveness_host: {last_error()} (status {n})")
         if res.witness_len <= cap:

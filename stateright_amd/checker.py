@@ -193,7 +193,7 @@ class CheckerBuilder:
         self._opts.profile = int(bool(on))
         return self
 
-    def complete_liveness(self, on=True):
+    def complete_liveness(self, on=True, fairness=None):
         """Engine opt-in: the complete `eventually` check. `spawn_bfs`, like the
         reference, refutes an `eventually` property only at a terminal state reached with the
         property's bit still set, so it misses a counterexample through a state that was first reached
@@ -204,8 +204,21 @@ class CheckerBuilder:
         (`GpuBfsChecker.loop_start`, `liveness`), which `assert_discovery` then accepts. No fairness is
         assumed (a self-loop on a state where the property does not hold refutes it), the witness is
         not the shortest one, and `target_state_count`, partitions / comm, `symmetry_canonical` and
-        plugin models are refused at spawn. Off by default; with it off nothing changes."""
-        self._opts.liveness = int(bool(on))
+        plugin models are refused at spawn. Off by default; with it off nothing changes.
+
+        `fairness="progress"` (progress fairness): a successor equal to its state is no successor, so
+        an action that changes nothing (2pc's RmRcvCommitMsg at a Committed rm) is no step. A state is
+        then a sink if it is terminal or a stutter end (it has successors, all of them itself); the
+        witness never steps from a state to itself and ends at a terminal state, at a stutter end
+        (`liveness(name)["end_kind"] == 3`) or by closing a loop of at least two distinct states. No
+        discovery then means: the property holds on every maximal path that does not stay forever
+        in one state that has a successor other than itself. It is NOT per-action weak fairness: a
+        cycle through two or more distinct states still refutes the property. The same refusals
+        apply; the simulation checker's `detect_loops` is unaffected (a self-loop closes a lasso
+        there). Any other `fairness` but None raises ValueError."""
+        if fairness is not None and fairness != "progress":
+            raise ValueError(f'complete_liveness: fairness must be None or "progress", not {fairness!r}')
+        self._opts.liveness = 0 if not on else N.SR_LIVENESS_PROGRESS if fairness == "progress" else N.SR_LIVENESS_COMPLETE
         return self
 
     def verbose(self, on=True):
@@ -353,6 +366,7 @@ class GpuBfsChecker:
         else:
             self._h = lib.sr_gpu_bfs_spawn(model.MODEL_ID, arr, len(params), ctypes.byref(opts))
         self._liveness = bool(opts.liveness)
+        self._progress = opts.liveness == N.SR_LIVENESS_PROGRESS
         self._spawned("sr_gpu_bfs_spawn")
 
     def _spawned(self, what):
@@ -545,7 +559,9 @@ class GpuBfsChecker:
         or the search did not explore everything), not_p_states (reachable states where the condition
         does not hold), surviving (those from which a path exists on which it never holds), rounds (an
         implementation detail), examined, witness_len (steps; -1 without a witness), loop_start (-1:
-        none, or a terminal witness), init_index (-1: the property holds) and pass_ms."""
+        none, or a witness that closes no loop), end_kind (0 no witness, 1 it ends at a terminal state,
+        2 it closes a loop, 3 it ends at a stutter end: progress fairness only), init_index (-1: the
+        property holds) and pass_ms."""
         r = N.sr_live_result()
         st = self._lib.sr_gpu_bfs_liveness(self._h, self._prop_index(name), ctypes.byref(r))
         if st != 0:
@@ -650,13 +666,26 @@ class GpuBfsChecker:
         """Whether this check can report a lasso for an `eventually` property (`complete_liveness()`)."""
         return self._liveness
 
+    def _accepts_stutter_ends(self):
+        """Whether this check ran under progress fairness (`complete_liveness(fairness="progress")`)."""
+        return getattr(self, "_progress", False)
+
+    def _sink_kind(self, actions, init):
+        """The host model's answer for the state the actions lead to from init state `init`: 0 it has a
+        successor other than itself, 1 terminal, 3 a stutter end (-1: no such path)."""
+        ids = [self.action_id(a) for a in actions]
+        arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
+        return self._lib.sr_gpu_bfs_sink_kind(self._h, init, arr, len(ids))
+
     def assert_discovery(self, name, actions):
         """`assert_discovery` (src/checker.rs:292-337): the actions, from some init state, lead to a
         state violating an `always` / satisfying a `sometimes` property, or along a path on which
         an `eventually` property never holds and that ends at a terminal state. Only a check that can
         report lassos (`complete_liveness()`; the simulation checker's `detect_loops=True`) also accepts,
         for an `eventually` property, a path that ends at a state equal to an earlier state of the
-        path: the cycle between them can repeat forever."""
+        path: the cycle between them can repeat forever. A check under progress fairness also accepts,
+        for an `eventually` property, a path that ends at a stutter end (a state with successors that
+        all are the state itself), decided on the host model."""
         found = self.assert_any_discovery(name)
         i = self._prop_index(name)
         exp = self.properties()[i][1]
@@ -678,6 +707,8 @@ class GpuBfsChecker:
                 if loops:
                     states, _ = self.replay(actions, init)
                     closed = states[-1] in states[:-1]
+                if not terminal and not closed and self._accepts_stutter_ends():
+                    closed = self._sink_kind(actions, init) == N.SR_LIVE_END_STUTTER
                 if not satisfied and (terminal or closed):
                     return
                 if satisfied:

@@ -42,6 +42,7 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_SPREAD:
         case SR_MODEL_LIVE_GRAPH:
             return reg_spread(a);
+        case SR_MODEL_2PC_LIVE: return reg_two_phase_live(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
@@ -436,6 +437,8 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             return with_spread_model(p, np, [&](const auto& m) -> i64 { return f(m); });
         case SR_MODEL_LIVE_GRAPH:
             return with_live_graph(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_2PC_LIVE:
+            return with_two_phase_live(p, np, [&](const auto& m) -> i64 { return f(m); });
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -667,12 +670,29 @@ int32_t sr_gpu_bfs_liveness(const sr_bfs* b, int32_t prop, sr_live_result* out) 
 
 int64_t sr_liveness_host(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_live_result* out,
                          int64_t* action_ids, int32_t cap) {
+    return sr_liveness_host_fair(model, p, np, prop, 0, max_states, out, action_ids, cap);
+}
+
+int32_t sr_gpu_bfs_sink_kind(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n) {
+    if (!b || n < 0 || (n > 0 && !ids)) return -1;
+    return b->e->sink_kind(init, ids, n);
+}
+
+int64_t sr_liveness_host_fair(int32_t model, const int64_t* p, int32_t np, int32_t prop, int32_t fairness, int64_t max_states,
+                              sr_live_result* out, int64_t* action_ids, int32_t cap) {
     try {
         if (!out || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host: out and max_states >= 1");
+        if (fairness != 0 && fairness != 1) throw Error(SR_ERR_ARG, "sr_liveness_host_fair: fairness must be 0 (none) or 1 (progress)");
+        // SR_LIVE_MOVES=0: the progress mode compares states even where the model's `enabled_moves` names
+        // its self-loops (tests run both and compare; read per call)
+        const char* e = std::getenv("SR_LIVE_MOVES");
+        const bool moves = !e || std::atoi(e) != 0;
         const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
             using M = std::decay_t<decltype(m)>;
             if constexpr (has_emask<M>::value) {
-                const LiveHost h = live_host(m, prop, (u64)max_states);
+                const LiveHost h = !fairness ? live_host(m, prop, (u64)max_states)
+                                   : moves   ? live_host<true, true>(m, prop, (u64)max_states)
+                                             : live_host<true, false>(m, prop, (u64)max_states);
                 *out = h.r;
                 for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
                 return (i64)h.unique;

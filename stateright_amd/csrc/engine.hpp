@@ -74,6 +74,11 @@ class EngineBase {
                        std::vector<int>* all_conds = nullptr, int* terminal = nullptr) const = 0;
     virtual int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                         std::vector<i64>& states) const = 0;
+    // The sink kind of the state the actions lead to from init state `init` (sr_gpu_bfs_sink_kind).
+    virtual int sink_kind(int init, const i64* ids, int n) const {
+        (void)init, (void)ids, (void)n;
+        return -1;
+    }
     // The complete `eventually` check's outcome for property p (live.hpp); false: p is no property.
     virtual bool live_result(int p, sr_live_result* out) const {
         if (p < 0 || p >= nprops()) return false;
@@ -110,6 +115,29 @@ std::vector<u64> init_states_of(const M& m) {
                                     " init states must report init_count())");
     v.resize((size_t)k * M::W);
     return v;
+}
+
+// The sink kind (sr_gpu_bfs_sink_kind) of the state that the canonical action ids lead to from init
+// state `init`, steps matched as replay_model matches them: -1 no such path, 0 the state has a
+// successor other than itself, SR_LIVE_END_TERMINAL no successor, SR_LIVE_END_STUTTER successors, all itself.
+template <class M>
+int sink_kind_model(const M& m, int init, const i64* ids, int n) {
+    constexpr int W = M::W;
+    const std::vector<u64> inits = init_states_of(m);
+    if (init < 0 || init >= (int)(inits.size() / W)) return -1;
+    std::vector<u64> cur(&inits[(size_t)init * W], &inits[(size_t)init * W] + W);
+    for (int i = 0; i < n; ++i) {
+        bool found = false;
+        std::vector<u64> nx;
+        for_each_successor(m, cur.data(), [&](int a, const u64* ns) {
+            if (!found && m.action_id(cur.data(), a) == ids[i]) nx.assign(ns, ns + W), found = true;
+        });
+        if (!found) return -1;
+        cur = nx;
+    }
+    u64 all = 0, other = 0;
+    for_each_successor(m, cur.data(), [&](int, const u64* ns) { ++all, other += !std::equal(cur.begin(), cur.end(), ns); });
+    return other ? 0 : all ? SR_LIVE_END_STUTTER : SR_LIVE_END_TERMINAL;
 }
 
 template <class M>
@@ -454,6 +482,7 @@ class Engine final : public EngineBase {
                std::vector<int>* all_conds, int* terminal) const override {
         return replay_model(base_model(m_), init, ids, n, states, conds, all_conds, terminal);
     }
+    int sink_kind(int init, const i64* ids, int n) const override { return sink_kind_model(base_model(m_), init, ids, n); }
     int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                 std::vector<i64>& states) const override {
         return explore_model(base_model(m_), fps, n, action, has, fp, states);
@@ -1328,6 +1357,8 @@ class Engine final : public EngineBase {
     // until a round removes nothing (one counter read-back per round, as for a level; the worklist
     // shrinks, so later rounds are cheap), and if an init state survived, the witness by live_walk.
     // The arena is R, the final visited set names its states. Every buffer lives for this call only.
+    // sr_opts.liveness = SR_LIVENESS_PROGRESS launches the FAIR instantiations of live_trim and
+    // live_walk (progress fairness, live.hpp); every other value launches the plain ones.
     void live_pass() {
         live.assign(M::NPROPS, live_result_none());
         if constexpr (has_emask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
@@ -1338,6 +1369,7 @@ class Engine final : public EngineBase {
             if (lstart_.back() > 0xffffffffull)
                 throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
             const u32 n = (u32)lstart_.back();
+            const bool fair = o_.liveness == SR_LIVENESS_PROGRESS;
             const TableView t = view();
             const size_t bwords = (size_t)((cap_ + 31) / 32);
             DBuf<u64> slot_of, lcb, out;
@@ -1381,8 +1413,12 @@ class Engine final : public EngineBase {
                     h.next_n = h.removed = 0;
                     if (cnt) {
                         SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
-                        live_trim<M><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of.p, alive.p, wl[cur].p,
-                                                                                             cnt, wl[cur ^ 1].p, lc);
+                        if (fair)
+                            live_trim<M, true><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of.p, alive.p,
+                                                                                                       wl[cur].p, cnt, wl[cur ^ 1].p, lc);
+                        else
+                            live_trim<M><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of.p, alive.p, wl[cur].p,
+                                                                                                 cnt, wl[cur ^ 1].p, lc);
                         read_back();
                     }
                     r.surviving -= h.removed;
@@ -1405,7 +1441,8 @@ class Engine final : public EngineBase {
                     SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
                     for (u32 resume = 0;; resume = 1) {  // (each launch but the last takes walk_steps steps; |F_p| in all)
                         SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
-                        live_walk<M><<<1, 64, 0, stream_>>>(m_, t, alive.p, onpath.p, out.p, walk_steps, resume, lc);
+                        if (fair) live_walk<M, true><<<1, 64, 0, stream_>>>(m_, t, alive.p, onpath.p, out.p, walk_steps, resume, lc);
+                        else live_walk<M><<<1, 64, 0, stream_>>>(m_, t, alive.p, onpath.p, out.p, walk_steps, resume, lc);
                         read_back();
                         if (h.steps > walk_steps) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
                         const size_t o = path.size();
@@ -1418,7 +1455,8 @@ class Engine final : public EngineBase {
                         if (!h.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
                         SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)h.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
                     }
-                    live_accept(p, r, path, h.end == LIVE_WALK_LOOP);
+                    if (h.end == LIVE_WALK_STUTTER && !fair) throw Error(SR_ERR_HIP, "liveness: a witness ends at a stutter end with the mode off");
+                    live_accept(p, r, path, h.end, fair);
                 }
                 r.pass_ms = secs(t0, Clock::now()) * 1e3;
             }
@@ -1429,8 +1467,10 @@ class Engine final : public EngineBase {
     // step is a successor in `actions()` order (concrete_path), the condition of p holds on no state,
     // and the path ends at a terminal state or (lasso) at a state EQUAL, word for word, to an earlier
     // one; the device ended the walk on equal visited-set slots, which in fingerprint mode are equal
-    // 64-bit fingerprints.
-    void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, bool lasso) {
+    // 64-bit fingerprints. Under progress fairness (fair) also: no step returns its own state, and a
+    // path that is no lasso ends at a terminal state or at a stutter end, which has at least one
+    // successor and whose successors all are the state itself.
+    void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, u32 end, bool fair) {
         const size_t len = path.size() / W - 1;
         const std::string name = m_.prop_name(p);
         std::vector<i64> acts, described;
@@ -1438,18 +1478,32 @@ class Engine final : public EngineBase {
         for (size_t i = 0; i <= len; ++i)
             if (!live_not_p(m_, p, &path[i * W]))
                 throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
+        if (fair)
+            for (size_t i = 0; i < len; ++i)
+                if (std::equal(&path[i * W], &path[i * W] + W, &path[(i + 1) * W]))
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: step " + std::to_string(i) + " of the witness of \"" + name +
+                                                           "\" returns its own state (progress fairness steps over no self-loop)");
         const u64* last = &path[len * W];
-        if (lasso) {
+        if (end == LIVE_WALK_LOOP) {
             size_t j = 0;
             while (j < len && !std::equal(last, last + W, &path[j * W])) ++j;
             if (j == len)
                 throw Error(SR_ERR_NONDETERMINISM, "liveness: fingerprint collision: the witness of \"" + name + "\" ended as a loop at step " +
                                                        std::to_string(len) + ", but its state there equals no earlier state of the path");
             r.loop_start = (int64_t)j;
+            r.end_kind = SR_LIVE_END_LOOP;
         } else {
-            bool any = false;
-            for_each_successor(m_, last, [&](int, const u64*) { any = true; });
-            if (any) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness of \"" + name + "\" ends at a state that is not terminal");
+            u64 all = 0, other = 0;
+            for_each_successor(m_, last, [&](int, const u64* ns) { ++all, other += !std::equal(last, last + W, ns); });
+            if (end == LIVE_WALK_STUTTER) {
+                if (!all || other)
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness of \"" + name + "\" ends at a state that is no stutter end (" +
+                                                           std::to_string(all) + " successors, " + std::to_string(other) + " of them other states)");
+                r.end_kind = SR_LIVE_END_STUTTER;
+            } else {
+                if (all) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness of \"" + name + "\" ends at a state that is not terminal");
+                r.end_kind = SR_LIVE_END_TERMINAL;
+            }
         }
         r.witness_len = (int64_t)len;
         live_path_[p] = path;

@@ -27,6 +27,13 @@
 // lanes per workgroup and as many workgroups as the worklist has entries for. Worklists hold 4-byte
 // arena indices and are appended per wave with one atomic (live_append, wave_append's aggregation
 // for an index instead of a staged state).
+// live_trim and live_walk are instantiated for both values of live_step's FAIR switch (progress
+// fairness, live.hpp); live_mark and live_first_init do not step and are shared. With FAIR a stutter
+// end (every successor is the state itself) keeps its bit and leaves the worklist for good, like a
+// terminal state, and the walk ends there with LIVE_WALK_STUTTER; the FAIR = false instantiations are
+// the kernels as they were, and the only ones launched with the mode off. FAIR adds a W-word compare
+// per successor (none for a model whose `enabled_moves` names its self-loops exactly), no LDS and no
+// lookup: the trim stays bound by the latency of its dependent lookups.
 #pragma once
 
 namespace sr {
@@ -38,7 +45,7 @@ enum LiveErr : u32 {
     LIVE_ERR_LOOKUP = 1,  // find_slot did not find a reachable state or a successor of one
     LIVE_ERR_STUCK = 2,   // a state of the fixpoint with successors, none of them alive
 };
-enum LiveWalkEnd : u32 { LIVE_WALK_MORE = 0, LIVE_WALK_TERMINAL = 1, LIVE_WALK_LOOP = 2 };
+enum LiveWalkEnd : u32 { LIVE_WALK_MORE = 0, LIVE_WALK_TERMINAL = 1, LIVE_WALK_LOOP = 2, LIVE_WALK_STUTTER = 3 };
 
 struct LiveCounters {
     u32 next_n;   // entries appended to the worklist being written
@@ -88,7 +95,7 @@ __global__ void __launch_bounds__(LIVE_BLOCK) live_mark(M m, const u64* __restri
 }
 
 // next has room for n entries (it takes a subset of wl's).
-template <class M>
+template <class M, bool FAIR = false>
 __global__ void __launch_bounds__(LIVE_BLOCK) live_trim(M m, const u64* __restrict__ arena, TableView t,
                                                         const u64* __restrict__ slot_of, u32* alive,
                                                         const u32* __restrict__ wl, u32 n, u32* __restrict__ next,
@@ -101,7 +108,7 @@ __global__ void __launch_bounds__(LIVE_BLOCK) live_trim(M m, const u64* __restri
         u64 s[M::W], out[M::W];
         load_state<M::W>(arena, idx, s);
         bool lost = false;
-        const int r = live_step(
+        const int r = live_step<FAIR>(
             m, s,
             [&](const u64* ns) {
                 const u64 sl = find_slot(t, probe_key(m, t, ns));
@@ -114,7 +121,7 @@ __global__ void __launch_bounds__(LIVE_BLOCK) live_trim(M m, const u64* __restri
             out);
         if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
         keep = r >= 0;
-        dead = r == LIVE_DEAD;
+        dead = r == LIVE_DEAD;  // (LIVE_TERMINAL, LIVE_STUTTER: a sink, neither kept nor dead)
         if (dead) {
             const u64 sl = slot_of[idx];
             atomicAnd(&alive[sl >> 5], ~(1u << (sl & 31)));
@@ -137,8 +144,10 @@ __global__ void __launch_bounds__(LIVE_BLOCK) live_first_init(const u64* __restr
 
 // One wave. out holds max_steps + 1 states: out[0] is the state to go on from (resume = 0: the
 // walk's first state, marked on the path here; 1: the last state of the previous launch), state
-// k + 1 the one step k reached. lc->steps / lc->end say where and why the launch stopped.
-template <class M>
+// k + 1 the one step k reached. lc->steps / lc->end say where and why the launch stopped. FAIR: the
+// wave ends TERMINAL only if no lane saw any successor, STUTTER if none found a successor other than
+// the state itself and some lane saw the state itself; LIVE_ERR_STUCK means what it meant.
+template <class M, bool FAIR = false>
 __global__ void __launch_bounds__(64) live_walk(M m, TableView t, const u32* alive, u32* onpath, u64* out, u32 max_steps,
                                                 u32 resume, LiveCounters* lc) {
     constexpr int W = M::W;
@@ -156,7 +165,7 @@ __global__ void __launch_bounds__(64) live_walk(M m, TableView t, const u32* ali
     while (!err && k < max_steps) {  // (every condition below is wave-uniform)
         u64 nx[W];
         bool lost = false;
-        const int r = live_step(
+        const int r = live_step<FAIR>(
             m, cur,
             [&](const u64* ns) {
                 const u64 sl = find_slot(t, probe_key(m, t, ns));
@@ -176,6 +185,7 @@ __global__ void __launch_bounds__(64) live_walk(M m, TableView t, const u32* ali
         for (int o = 32; o; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
         if (best == 0x7fffffff) {
             if (__ballot(r == LIVE_DEAD)) err |= LIVE_ERR_STUCK;
+            else if (FAIR && __ballot(r == LIVE_STUTTER)) end = LIVE_WALK_STUTTER;
             else end = LIVE_WALK_TERMINAL;
             break;
         }

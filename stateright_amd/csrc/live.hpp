@@ -23,6 +23,26 @@
 // walk follows a function on a finite set, so it ends within |F_p| steps. It is not the shortest
 // counterexample.
 //
+// PROGRESS FAIRNESS (opt-in: sr_opts.liveness = SR_LIVENESS_PROGRESS, `complete_liveness(fairness=
+// "progress")`): the same rule over the graph without its self-loops, so that an action that leaves
+// the state as it is ("nothing changed": 2pc's RmRcvCommitMsg at a Committed rm) is no step.
+//   succ'(s)      succ(s) \ {s}: a successor whose W words all equal those of s is no successor;
+//   terminal'(s)  succ'(s) is empty: s is terminal (succ(s) is empty), or a STUTTER END (succ(s) is
+//                 not empty and every member is s). Both are sinks: a run that can only stutter stays
+//                 there legitimately;
+//   N_p           as above;
+//   F_p'          the greatest subset of N_p in which every state is terminal' or has a successor in
+//                 succ'(s) and F_p'.
+// The witness steps over succ' only: from the init state of lowest index in F_p', the lowest slot
+// whose result differs from s_t and is in F_p', to a terminal' state (loop_start = -1) or the first
+// repeated state, so a closed loop has at least two distinct states. No discovery then means: p holds
+// on every maximal path that does not stay forever in ONE state that has a successor other than
+// itself. It is NOT per-action weak fairness: a cycle through two or more distinct states still
+// refutes p, however unfair the run round it is; fair strongly connected components are not built
+// (DESIGN.md §10). The simulation checker's loop detection is not changed (a self-loop still closes
+// a lasso there), and what the plain mode refuses (plugins, partitions, symmetry,
+// target_state_count) this mode refuses too.
+//
 // The per-state rule and the witness step are ONE function, live_step below, which the kernels
 // (kernels_live.hpp: live_trim, live_walk) and the host form (live_host, the sr_liveness_host entry
 // point) instantiate; they differ only in how "is this successor in the set" is answered (the alive
@@ -39,7 +59,7 @@
 
 namespace sr {
 
-enum LiveStep : int { LIVE_TERMINAL = -1, LIVE_DEAD = -2 };
+enum LiveStep : int { LIVE_TERMINAL = -1, LIVE_DEAD = -2, LIVE_STUTTER = -3 };
 
 // Whether s is in N_p (p an `eventually` property: discovers() is its condition).
 template <class M>
@@ -47,25 +67,63 @@ SR_HD bool live_not_p(const M& m, int p, const u64* s) {
     return !m.discovers(p, s);
 }
 
+template <int W>
+SR_HD bool live_same(const u64* a, const u64* b) {
+    bool eq = true;
+#pragma unroll
+    for (int i = 0; i < W; ++i) eq = eq && a[i] == b[i];
+    return eq;
+}
+
+// Whether the model's own hook names its self-loops exactly (2pc: `enabled_moves` leaves the slots
+// that change the state, and only those), so that the progress mode need not compare states.
+template <class M>
+constexpr bool live_moves_model = exact_moves_model<M> && has_enabled_moves<M>::value;
+
 // The successors of s in slot order, among the enabled slots of rank first, first + stride, ...
 // (stride a power of two; the host and live_trim take all of them: 0, 1; the lanes of live_walk
 // share them: lane, 64), up to the first one for which alive(ns) holds. Returns that slot, with
 // the successor in out; else LIVE_DEAD if some slot had a successor, LIVE_TERMINAL if none had.
-template <class M, class Alive>
+// FAIR (progress fairness, above): a successor equal to s is skipped and is no successor; with none
+// left the result is LIVE_STUTTER if a slot gave s itself (among ALL enabled slots where the model's
+// hook counts them, among this call's share of them otherwise), LIVE_TERMINAL if no slot gave
+// anything. MOVES = false compares the states even where the model's hook would answer (tests).
+template <bool FAIR = false, bool MOVES = true, class M, class Alive>
 SR_HD int live_step(const M& m, const u64* s, Alive&& alive, u64* out, u32 first = 0, u32 stride = 1) {
     u64 mask[M::MW];
-    m.enabled(s, mask);
     bool any = false;
     u32 r = 0;
-    for (int w = 0; w < M::MW; ++w)
-        for (u64 bits = mask[w]; bits; bits &= bits - 1, ++r) {
-            if ((r & (stride - 1)) != first) continue;
-            const int a = w * 64 + __builtin_ctzll(bits);
-            if (!m.apply(s, a, out)) continue;
-            any = true;
-            if (alive(out)) return a;
-        }
-    return any ? LIVE_DEAD : LIVE_TERMINAL;
+    if constexpr (!FAIR) {
+        m.enabled(s, mask);
+        for (int w = 0; w < M::MW; ++w)
+            for (u64 bits = mask[w]; bits; bits &= bits - 1, ++r) {
+                if ((r & (stride - 1)) != first) continue;
+                const int a = w * 64 + __builtin_ctzll(bits);
+                if (!m.apply(s, a, out)) continue;
+                any = true;
+                if (alive(out)) return a;
+            }
+        return any ? LIVE_DEAD : LIVE_TERMINAL;
+    } else {
+        bool self = false;
+        if constexpr (MOVES && live_moves_model<M>) self = m.enabled_moves(s, mask) != 0;
+        else m.enabled(s, mask);
+        for (int w = 0; w < M::MW; ++w)
+            for (u64 bits = mask[w]; bits; bits &= bits - 1, ++r) {
+                if ((r & (stride - 1)) != first) continue;
+                const int a = w * 64 + __builtin_ctzll(bits);
+                if (!m.apply(s, a, out)) continue;
+                if constexpr (!(MOVES && live_moves_model<M>)) {
+                    if (live_same<M::W>(out, s)) {
+                        self = true;
+                        continue;
+                    }
+                }
+                any = true;
+                if (alive(out)) return a;
+            }
+        return any ? LIVE_DEAD : self ? LIVE_STUTTER : LIVE_TERMINAL;
+    }
 }
 
 inline sr_live_result live_result_none() {
@@ -87,7 +145,8 @@ template <class M>
 std::vector<u64> init_states_of(const M& m);  // (engine.hpp)
 
 // The check on the host, with no device: a search over at most max_states states, the fixpoint (in
-// place, worklist by worklist as the device runs it) and the witness.
+// place, worklist by worklist as the device runs it) and the witness. FAIR: progress fairness; MOVES:
+// see live_step.
 struct LiveHost {
     sr_live_result r = live_result_none();
     u64 unique = 0;
@@ -95,7 +154,7 @@ struct LiveHost {
     std::vector<i64> actions;  // its canonical action ids, one per step
 };
 
-template <class M>
+template <bool FAIR = false, bool MOVES = true, class M>
 LiveHost live_host(const M& m, int p, u64 max_states) {
     constexpr int W = M::W;
     if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
@@ -152,7 +211,7 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
         h.r.rounds += 1;
         h.r.examined += wl.size();
         for (u32 i : wl) {
-            const int a = live_step(m, st[i].data(), is_alive, out);
+            const int a = live_step<FAIR, MOVES>(m, st[i].data(), is_alive, out);
             if (a >= 0) next.push_back(i);
             else if (a == LIVE_DEAD) alive[i] = 0, ++removed;
         }
@@ -171,12 +230,14 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
             if (seen != at.end()) {
                 h.r.witness_len = t;
                 h.r.loop_start = seen->second;
+                h.r.end_kind = SR_LIVE_END_LOOP;
                 break;
             }
             at.emplace(cur, t);
-            const int a = live_step(m, st[cur].data(), is_alive, out);
-            if (a == LIVE_TERMINAL) {
+            const int a = live_step<FAIR, MOVES>(m, st[cur].data(), is_alive, out);
+            if (a == LIVE_TERMINAL || a == LIVE_STUTTER) {
                 h.r.witness_len = t;
+                h.r.end_kind = a == LIVE_TERMINAL ? SR_LIVE_END_TERMINAL : SR_LIVE_END_STUTTER;
                 break;
             }
             if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a state of the fixpoint has no successor in it");

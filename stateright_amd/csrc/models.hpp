@@ -624,6 +624,29 @@ struct TwoPhaseT {
 using TwoPhase = TwoPhaseT<0>;
 
 // -----------------------------------------------------------------------------------------------
+// TwoPhaseLive(n): two-phase commit with two `eventually` properties after its three (no reference
+// counterpart; the model of the complete `eventually` check's progress mode, live.hpp). State,
+// slots, `apply` and every hook are TwoPhase's, so `action_masks`, `enabled_moves` and
+// SELF_LOOPS_EXACT hold for it as they do there (unlike Canon / EvBits, which replace `apply`), and
+// its counts are 2pc's. 2pc has NO terminal state: once Commit or Abort is in msgs, RmRcvCommitMsg /
+// RmRcvAbortMsg stay enabled for ever as self-loops, so the search's own rule never refutes these
+// properties and the plain complete check refutes every one by stuttering.
+//   3  eventually "every RM decides": every rm is Committed or Aborted (holds under progress fairness)
+//   4  eventually "every RM commits": refuted by a path to the all-aborted stutter end
+// -----------------------------------------------------------------------------------------------
+struct TwoPhaseLive : TwoPhase {
+    static constexpr int NPROPS = 5;
+    u32 emask() const { return 3u << 3; }
+    SR_HD bool discovers(int p, const u64* sp) const {
+        if (p < 3) return TwoPhase::discovers(p, sp);
+        const u64 ev = even_mask(), hi = (sp[0] >> 1) & ev, lo = sp[0] & ev;
+        return p == 3 ? hi == ev : (hi & ~lo) == ev;  // rm_state 2 or 3 everywhere; 2 everywhere
+    }
+    int expectation(int p) const { return p < 3 ? TwoPhase::expectation(p) : EVENTUALLY; }
+    const char* prop_name(int p) const { return p < 3 ? TwoPhase::prop_name(p) : p == 3 ? "every RM decides" : "every RM commits"; }
+};
+
+// -----------------------------------------------------------------------------------------------
 // Ladder(K, F): a test fixture (no reference counterpart) for models with `action_masks` whose slot
 // count passes 64, where a table held one slot per lane and a one-word mask both end. K rungs are
 // climbed in order and F free bits are set in any order: (K + 1) * 2^F states, depth K + F.

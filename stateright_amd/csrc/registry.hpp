@@ -54,6 +54,16 @@ std::unique_ptr<EngineBase> reg_ping_pong(const EngineArgs& a);       // ping-po
 std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 slots) and the single-copy register
 std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
 std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4), LiveGraph
+std::unique_ptr<EngineBase> reg_two_phase_live(const EngineArgs& a);  // 2pc with `eventually` properties (TwoPhaseLive)
+
+// TwoPhaseLive (models.hpp) of (rm_count), handed to f: the engines (reg_two_phase_live.hip) and the
+// host-only entry points (engine.hip) validate alike.
+template <class F>
+auto with_two_phase_live(const i64* p, int np, F&& f) {
+    if (np < 1) throw Error(SR_ERR_ARG, "2pc-live needs 1 param (rm_count)");
+    if (p[0] < 1 || p[0] > 14) throw Error(SR_ERR_UNSUPPORTED, "2pc-live: rm_count must be in 1..=14 (4n+4 <= 63 bits)");
+    return f(TwoPhaseLive{{(int)p[0], 0}});
+}
 
 // The LiveGraph fixture (models.hpp) of (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words
 // (default 1), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip)

@@ -44,6 +44,20 @@ class TwoPhaseSys(_Model):
         return [self.rm_count]
 
 
+class TwoPhaseLiveSys(_Model):
+    """`TwoPhaseSys` with two `eventually` properties after its three (csrc/models.hpp `TwoPhaseLive`; no
+    reference counterpart): "every RM decides" (every rm Committed or Aborted) and "every RM commits".
+    States, actions and counts are 2pc's. 2pc has no terminal state (RmRcvCommitMsg / RmRcvAbortMsg stay
+    enabled as self-loops), so only `complete_liveness(fairness="progress")` says anything about them."""
+    MODEL_ID = N.SR_MODEL_2PC_LIVE
+
+    def __init__(self, rm_count):
+        self.rm_count = rm_count
+
+    def params(self):
+        return [self.rm_count]
+
+
 class Increment(_Model):
     """`increment` example `State::new(n)` (examples/increment.rs:109-197)."""
     MODEL_ID = N.SR_MODEL_INCREMENT
