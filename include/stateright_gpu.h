@@ -80,19 +80,27 @@ enum sr_model_id {
                                      Optionally followed by (roots, dup): the init states are the subsets
                                      0 .. roots-1, then 0 .. dup-1 again; 1 <= roots <= 2^free_bits,
                                      dup <= roots, roots + dup <= 512 (default 1, 0) */
-    SR_MODEL_LIVE_GRAPH = 15,     /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512[, words]) test fixture with
+    SR_MODEL_LIVE_GRAPH = 15,     /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512[, words[, dup]]) test fixture with
                                      cycles: states v < 2^n_bits; r(v, k) = fmix64(fmix64(seed ^ v) + k) (murmur3's
                                      finalizer); v has no actions iff t_mod > 0 and r(v, degree) % t_mod == 0, else
                                      slot k < degree leads to r(v, k) mod 2^n_bits (action id k); one `eventually`
                                      property "marked": p_mod > 0 and r(v, degree + 1) % p_mod == 0; init states
                                      0 .. roots-1; words = 1 (default), 2 or 4 pads the state with words that are
-                                     functions of v (stateright_amd/csrc/models.hpp LiveGraph) */
-    SR_MODEL_2PC_LIVE = 16        /* (rm_count<=14) SR_MODEL_2PC (same states, action slots and counts) with two
+                                     functions of v; dup (default 0, <= roots, roots + dup <= 512) repeats the init
+                                     states 0 .. dup-1 after the roots (stateright_amd/csrc/models.hpp LiveGraph) */
+    SR_MODEL_2PC_LIVE = 16,       /* (rm_count<=14) SR_MODEL_2PC (same states, action slots and counts) with two
                                      `eventually` properties after its three: 3 "every RM decides" (every rm is
                                      Committed or Aborted), 4 "every RM commits". No reference counterpart: 2pc
                                      has no terminal state (once Commit or Abort is sent, RmRcvCommitMsg /
                                      RmRcvAbortMsg stay enabled as self-loops), so it is the model of the complete
                                      `eventually` check's progress mode (SR_LIVENESS_PROGRESS) */
+    SR_MODEL_SPIN_LOCK = 17       /* (threads 1..20) n threads take a lock in turn while a clock ticks; one word:
+                                     holder (0 free, i + 1) in bits [0,5), served (n bits) from bit 5, tick above.
+                                     Slot i < n Acquire(i) (the lock is free), n + i Release(i) (thread i holds it:
+                                     serves i and frees the lock), 2n Tick (always: flips tick); (n + 1) 2^n 2 states.
+                                     Two `eventually` properties: 0 "some thread served", 1 "every thread served".
+                                     No reference counterpart: the model of the complete `eventually` check's
+                                     weak-fairness mode (SR_LIVENESS_WEAK) */
 };
 
 /* Visit order inside a BFS level. */
@@ -102,12 +110,15 @@ enum sr_order {
     SR_ORDER_FAST = 2  /* any order inside a level: wave-aggregated append, no ordering pass  */
 };
 
-/* sr_opts.liveness: the complete `eventually` check (see sr_gpu_bfs_liveness below). Every value but 0
- * and SR_LIVENESS_PROGRESS is read as SR_LIVENESS_COMPLETE. */
+/* sr_opts.liveness: the complete `eventually` check (see sr_gpu_bfs_liveness below). Every value but 0,
+ * SR_LIVENESS_PROGRESS and SR_LIVENESS_WEAK is read as SR_LIVENESS_COMPLETE. */
 enum sr_liveness_mode {
     SR_LIVENESS_OFF = 0,
     SR_LIVENESS_COMPLETE = 1, /* no fairness: a self-loop on a state where the property does not hold refutes it */
-    SR_LIVENESS_PROGRESS = 2  /* progress fairness: a successor equal to its state is no successor */
+    SR_LIVENESS_PROGRESS = 2, /* progress fairness: a successor equal to its state is no successor */
+    SR_LIVENESS_WEAK = 3      /* weak fairness per action slot (see sr_gpu_bfs_liveness_weak below). Until this
+                                 value was given its meaning, 3 was one of the "other values" read as
+                                 SR_LIVENESS_COMPLETE; the values from 4 up still are */
 };
 /* sr_live_result.end_kind: how the witness ends (both modes). */
 enum sr_live_end { SR_LIVE_END_NONE = 0, SR_LIVE_END_TERMINAL = 1, SR_LIVE_END_LOOP = 2, SR_LIVE_END_STUTTER = 3 };
@@ -148,7 +159,8 @@ typedef struct sr_opts {
                                     representatives are not canonical (src/checker/dfs.rs:258-283) */
     int32_t reserved0;           /* what were 4 bytes of tail padding; never read                  */
     int32_t liveness;            /* 1 = the complete `eventually` check (see sr_gpu_bfs_liveness below); 2 = the
-                                    same under progress fairness (enum sr_liveness_mode); 0 = off,
+                                    same under progress fairness, 3 = under weak fairness per action
+                                    slot (enum sr_liveness_mode); 0 = off,
                                     and then nothing changes. The struct grew from 56 to 64 bytes for it: a
                                     caller whose struct_size is 56 is read as liveness = 0, whatever its
                                     padding holds                                                   */
@@ -325,7 +337,7 @@ void sr_gpu_bfs_free(sr_bfs* bfs);
  * least two distinct states. No discovery then means: the property holds on every maximal path that
  * does not stay forever in one state that has a successor other than itself. This is NOT per-action
  * weak fairness: a cycle through two or more distinct states still refutes the property, and that is
- * not repaired here. The refusals above apply unchanged; the simulation checker's loop detection
+ * not repaired in this mode (SR_LIVENESS_WEAK below is). The refusals above apply unchanged; the simulation checker's loop detection
  * (sr_sim_opts.loops) is not affected: there a self-loop still closes a lasso. */
 typedef struct sr_live_result {
     int32_t ran;            /* 1 = the pass ran for this property                                  */
@@ -361,6 +373,55 @@ int64_t sr_liveness_host_fair(int32_t model_id, const int64_t* params, int32_t n
  * a joined check's model: -1 the actions cannot be replayed, 0 the state has a successor other than
  * itself, 1 it is terminal, 3 it is a stutter end (what `assert_discovery` asks in the progress mode). */
 int32_t sr_gpu_bfs_sink_kind(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n);
+
+/* ---- WEAK FAIRNESS (liveness = SR_LIVENESS_WEAK = 3, off by default; live.hpp and DESIGN.md section 12
+ * have the definition) ----
+ * An action SLOT is a fairness class, for the models that say their slots are actions (DGraph, LiveGraph,
+ * 2pc and 2pc-live, SpinLock); every other model is refused at spawn with SR_ERR_UNSUPPORTED, as is
+ * everything the other modes refuse. me(s, a): slot a is enabled at s, yields a state, and that state
+ * differs from s. Over F_p' (progress fairness above) and its edges between distinct states, a strongly
+ * connected component of two or more states is FAIR iff for every slot a some member has not me(., a), or
+ * some member's a-step stays inside the component. goal = the sinks of F_p' (terminal states and stutter
+ * ends) and the members of fair components; FairF = the states of F_p' from which goal is reachable. The
+ * property has a counterexample iff an init state is in FairF; no discovery means it holds on every maximal
+ * run that is weakly fair to every slot (which subsumes progress fairness). The witness is deterministic:
+ * from the init state of lowest index in FairF along the lowest slot that lowers the distance to goal; at
+ * a sink it ends (end_kind 1 or 3, loop_start -1); otherwise a closed walk inside the fair component
+ * follows, which for every slot in order either passes a state where the slot is not moving-enabled or
+ * takes it (end_kind 2; the path's last state equals its state at loop_start = stem_len; the loop may pass
+ * a state more than once). sr_live_result keeps its meanings: not_p_states |N_p|, surviving |F_p'|,
+ * witness_len = stem_len + loop_len. Not strong fairness: a slot that is disabled again and again on a
+ * loop is not protected. */
+typedef struct sr_live_weak {
+    int32_t ran;              /* 1 = the pass ran for this property in this mode                      */
+    int32_t reserved0;
+    uint64_t cyclic_states;   /* F_p' without its sinks, trimmed to the states with a successor in it  */
+    uint64_t components;      /* strongly connected components of two or more states                  */
+    uint64_t fair_components;
+    uint64_t goal_states;     /* sinks of F_p' and members of fair components                         */
+    uint64_t fair_states;     /* |FairF|                                                              */
+    int64_t stem_len;         /* steps from the init state to the sink or into the fair component; -1 */
+    int64_t loop_len;         /* steps of the closed walk; 0 where the witness ends at a sink; -1      */
+    uint32_t scc_rounds;      /* implementation details (kernel rounds of the component search, of the  */
+    uint32_t reach_rounds;    /* rank fixpoints, and rank fixpoints run for the loop): never compare    */
+    uint32_t segments;        /* them                                                                   */
+    uint32_t reserved1;
+    double pass_ms;           /* wall time of what this mode adds to the pass for this property        */
+} sr_live_weak;
+/* The weak-fairness figures for property `prop` of a joined check (ran = 0: the check ran in another mode,
+ * or sr_gpu_bfs_liveness would say ran = 0). */
+int32_t sr_gpu_bfs_liveness_weak(const sr_bfs* bfs, int32_t prop, sr_live_weak* out);
+/* Host-only (no device needed): sr_liveness_host under weak fairness, by other algorithms than the
+ * device's (Tarjan's components, breadth-first ranks over predecessor lists). SR_ERR_UNSUPPORTED for a
+ * model whose slots are not fairness classes. */
+int64_t sr_liveness_host_weak(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int64_t max_states,
+                              sr_live_result* out, sr_live_weak* weak, int64_t* action_ids, int32_t cap);
+/* Host-only: whether the loop of a lasso is weakly fair. The canonical action ids are replayed from init
+ * state `init` of a joined check's model; the loop is the states from index loop_start to the last, which
+ * must equal the state at loop_start. 1: every slot is not moving-enabled at some state of the loop or
+ * taken by one of its steps; 0: it is not, or the loop is not closed or has no step; -1: the actions
+ * cannot be replayed, or the model's slots are not fairness classes. */
+int32_t sr_gpu_bfs_loop_fair(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n, int32_t loop_start);
 /* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
  * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds
  * them. The dump is int64s: [states, init states, properties, the init states' numbers..., then per

@@ -221,6 +221,22 @@ class CheckerBuilder:
         self._opts.liveness = 0 if not on else N.SR_LIVENESS_PROGRESS if fairness == "progress" else N.SR_LIVENESS_COMPLETE
         return self
 
+    def weak_fairness(self, on=True):
+        """Engine opt-in: the complete `eventually` check under WEAK FAIRNESS per action slot (DESIGN.md
+        section 12). Like `complete_liveness(fairness="progress")`, and further: a cycle refutes an
+        `eventually` property only if a run round it can be fair to every slot, where a slot that is
+        moving-enabled (enabled, and its step changes the state) at every state of the cycle must be
+        taken by it. So a clock that can always tick no longer refutes everything. A discovery made by
+        the pass ends at a terminal state or a stutter end, or is a lasso whose loop is weakly fair
+        (`liveness(name)["weak"]` has the figures; `assert_discovery` accepts a lasso only if the host
+        model finds its loop weakly fair). No discovery means: the property holds on every maximal run
+        that is weakly fair to every slot. Only models whose slots are actions take it (DGraph,
+        LiveGraph, TwoPhaseSys / TwoPhaseLiveSys, SpinLockSys); the others, and whatever
+        `complete_liveness` refuses, are refused at spawn. Not strong fairness. `on=False` turns the
+        complete check off."""
+        self._opts.liveness = N.SR_LIVENESS_WEAK if on else 0
+        return self
+
     def verbose(self, on=True):
         self._opts.verbose = int(bool(on))
         return self
@@ -366,7 +382,8 @@ class GpuBfsChecker:
         else:
             self._h = lib.sr_gpu_bfs_spawn(model.MODEL_ID, arr, len(params), ctypes.byref(opts))
         self._liveness = bool(opts.liveness)
-        self._progress = opts.liveness == N.SR_LIVENESS_PROGRESS
+        self._weak = opts.liveness == N.SR_LIVENESS_WEAK
+        self._progress = opts.liveness == N.SR_LIVENESS_PROGRESS or self._weak  # (weak fairness subsumes it)
         self._spawned("sr_gpu_bfs_spawn")
 
     def _spawned(self, what):
@@ -561,12 +578,23 @@ class GpuBfsChecker:
         implementation detail), examined, witness_len (steps; -1 without a witness), loop_start (-1:
         none, or a witness that closes no loop), end_kind (0 no witness, 1 it ends at a terminal state,
         2 it closes a loop, 3 it ends at a stutter end: progress fairness only), init_index (-1: the
-        property holds) and pass_ms."""
+        property holds) and pass_ms. A check under `weak_fairness()` adds "weak": the dict of sr_live_weak
+        (cyclic_states, components, fair_components, goal_states, fair_states, stem_len, loop_len, and the
+        round counters, which are implementation details); `surviving` is then |F_p'|, and `loop_start`
+        the state the last state repeats (the closed walk may pass it more than once)."""
         r = N.sr_live_result()
         st = self._lib.sr_gpu_bfs_liveness(self._h, self._prop_index(name), ctypes.byref(r))
         if st != 0:
             raise CheckerError("sr_gpu_bfs_liveness", st)
-        return r.as_dict()
+        out = r.as_dict()
+        if getattr(self, "_weak", False) and r.ran:
+            w = N.sr_live_weak()
+            st = self._lib.sr_gpu_bfs_liveness_weak(self._h, self._prop_index(name), ctypes.byref(w))
+            if st != 0:
+                raise CheckerError("sr_gpu_bfs_liveness_weak", st)
+            if w.ran:
+                out["weak"] = w.as_dict()
+        return out
 
     def loop_start(self, name):
         """`complete_liveness()`: if the discovery of the `eventually` property `name` is a lasso found
@@ -670,6 +698,12 @@ class GpuBfsChecker:
         """Whether this check ran under progress fairness (`complete_liveness(fairness="progress")`)."""
         return getattr(self, "_progress", False)
 
+    def _loop_is_fair(self, actions, init, loop_start):
+        """The host model's answer for the loop of a lasso (sr_gpu_bfs_loop_fair): True iff it is weakly fair."""
+        ids = [self.action_id(a) for a in actions]
+        arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
+        return self._lib.sr_gpu_bfs_loop_fair(self._h, init, arr, len(ids), loop_start) == 1
+
     def _sink_kind(self, actions, init):
         """The host model's answer for the state the actions lead to from init state `init`: 0 it has a
         successor other than itself, 1 terminal, 3 a stutter end (-1: no such path)."""
@@ -685,7 +719,8 @@ class GpuBfsChecker:
         for an `eventually` property, a path that ends at a state equal to an earlier state of the
         path: the cycle between them can repeat forever. A check under progress fairness also accepts,
         for an `eventually` property, a path that ends at a stutter end (a state with successors that
-        all are the state itself), decided on the host model."""
+        all are the state itself), decided on the host model. A check under weak fairness accepts stutter
+        ends likewise, and a lasso only if its loop is weakly fair on the host model."""
         found = self.assert_any_discovery(name)
         i = self._prop_index(name)
         exp = self.properties()[i][1]
@@ -707,6 +742,10 @@ class GpuBfsChecker:
                 if loops:
                     states, _ = self.replay(actions, init)
                     closed = states[-1] in states[:-1]
+                    if closed and getattr(self, "_weak", False):  # (weak fairness: only a weakly fair loop refutes)
+                        closed = self._loop_is_fair(actions, init, states.index(states[-1]))
+                        if not closed:
+                            info.append("incorrect counterexample closes a loop that is not weakly fair")
                 if not terminal and not closed and self._accepts_stutter_ends():
                     closed = self._sink_kind(actions, init) == N.SR_LIVE_END_STUTTER
                 if not satisfied and (terminal or closed):

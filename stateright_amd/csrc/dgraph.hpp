@@ -78,6 +78,7 @@ inline Tables& tables(const i64* p, int np, int device) {
 
 struct DGraph {
     static constexpr int W = 1, MW = 4, NPROPS = 1;
+    static constexpr bool FAIR_SLOTS = true;  // "go to node a" is one fairness class (live.hpp, weak fairness)
     int expect = EVENTUALLY;
     int max_deg = 0;
     const u64* adj_d = nullptr;

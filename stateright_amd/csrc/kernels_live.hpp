@@ -213,4 +213,434 @@ __global__ void __launch_bounds__(64) live_walk(M m, TableView t, const u32* ali
     }
 }
 
+// ---- weak fairness (live.hpp: WEAK FAIRNESS). Launched only with sr_opts.liveness = SR_LIVENESS_WEAK, after
+// live_mark and the progress trim (live_trim<M, true>), which run as they are. A state of N_p is named by
+// its arena index here: IDX maps a visited-set slot to the arena index that live_mark listed for it (~0 for
+// a slot outside N_p), so colours, component numbers and ranks are 4-byte arrays by arena index, and a
+// successor costs one find_slot and one IDX load. A component is named by its ROOT, the highest arena
+// index in it.
+//   live_index     IDX and the NP list's states; RANK 0 for the sinks of F_p' (alive, not in U).
+//   live_set_bits  the U bitmap from the trim's last worklist (F_p' minus its sinks); live_trim<M, true> on
+//                  that bitmap then leaves the states with a successor in U.
+//   live_colour_init / live_colour_push  forward max-colouring: every state of U starts with its arena
+//                  index and pushes its colour along succ' inside U with atomicMax; a state whose colour
+//                  rose is listed once per round (a round stamp) and pushes again in the next round.
+//   live_scc_seed / live_scc_join  a state whose colour is its own index is a root and joins its component;
+//                  s joins iff it has the root's colour and a successor in U that has joined (a backward
+//                  fixpoint evaluated forwards, all roots at once; joins are written in place, which only
+//                  lets a state join a round earlier). live_scc_leave clears the U bits of what joined.
+//   live_comp_acc  per member of a component: its size, the AND of the me masks and the OR of the slots whose
+//                  successor is a member. Lanes of a wave that share the component (the common case: a few
+//                  large components) reduce in registers and issue one atomic per word.
+//   live_goal      sinks and members of fair components of two or more states get rank 0; the other states
+//                  of F_p' are listed for live_reach; roots count the components.
+//   live_reach     one level of ranks towards rank 0 inside a domain (the states whose RANK entry is not
+//                  frozen at ~0 outside the list): a listed state joins in round r only through a successor
+//                  of rank < r, so ranks written in the same round are never read as a reason.
+//   live_members / live_targets  one component's members; a slot's target set inside it.
+//   live_first_ranked  the init state of lowest index with a rank.
+//   live_descend   one wave, lanes sharing the slots as live_walk does: the lowest rank-decreasing slot
+//                  down to rank 0, the states to `out`; accumulates the loop's "not moving-enabled
+//                  somewhere" and "taken" masks; bounded and resumable like live_walk.
+// All of them are bound by the latency of dependent lookups, as live_trim is; none uses LDS.
+
+constexpr int LIVE_MW_MAX = 4;  // mask words of a model in the weak mode (DGraph: 256 slots)
+
+enum LiveDescendEnd : u32 { LIVE_DESCEND_MORE = 0, LIVE_DESCEND_DONE = 1 };
+
+struct LiveWeakCounters {
+    u32 next_n;      // entries appended to the list being written
+    u32 joined;      // states that joined (a component, the ranked set) / bits set this round
+    u32 err;         // LiveErr
+    u32 steps;       // live_descend: steps taken by the launch
+    u32 end;         // live_descend: LiveDescendEnd
+    u32 first_init;  // live_first_ranked
+    u32 last_idx;    // live_descend: the arena index of the launch's last state
+    u32 comps, fair_comps, goal;
+    u64 notme[LIVE_MW_MAX], taken[LIVE_MW_MAX];  // live_descend: accumulated over launches (the host clears them)
+};
+
+// The arena index of the N_p state ns (a successor), ~0 if it is outside N_p; a failed lookup sets lost.
+template <class M>
+__device__ __forceinline__ u32 live_idx_of(const M& m, const TableView& t, const u32* __restrict__ idx, const u64* ns, bool& lost,
+                                           u64* slot = nullptr) {
+    const u64 sl = find_slot(t, probe_key(m, t, ns));
+    if (slot) *slot = sl;
+    if (sl == ~0ull) {
+        lost = true;
+        return ~0u;
+    }
+    return idx[sl];
+}
+
+__device__ __forceinline__ u32 live_load(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void live_store(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// np: live_mark's list (every slot of N_p once). u0: the bitmap of F_p' minus its sinks.
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_index(const u32* __restrict__ np, u32 n, const u64* __restrict__ slot_of,
+                                                         const u32* alive, const u32* u0, u32* __restrict__ idx,
+                                                         u32* __restrict__ rank) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    const u32 i = np[g];
+    const u64 sl = slot_of[i];
+    idx[sl] = i;
+    rank[i] = live_bit(alive, sl) && !live_bit(u0, sl) ? 0u : ~0u;
+}
+
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_set_bits(const u32* __restrict__ list, u32 n, const u64* __restrict__ slot_of,
+                                                            u32* bits) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    const u64 sl = slot_of[list[g]];
+    atomicOr(&bits[sl >> 5], 1u << (sl & 31));
+}
+
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_colour_init(const u32* __restrict__ list, u32 n, u32* __restrict__ colour) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g < n) colour[list[g]] = list[g];
+}
+
+// next has room for every state of U (a state is listed at most once per round: stamp[t] == round).
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_colour_push(M m, const u64* __restrict__ arena, TableView t,
+                                                               const u32* __restrict__ idx, const u32* u, u32* colour, u32* stamp,
+                                                               u32 round, const u32* __restrict__ wl, u32 n, u32* __restrict__ next,
+                                                               LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    const u32 i = wl[g];
+    u64 s[M::W], me[M::MW];
+    load_state<M::W>(arena, i, s);
+    const u32 c = live_load(&colour[i]);
+    bool lost = false;
+    live_moving(m, s, me, [&](int, const u64* ns) {
+        u64 sl;
+        const u32 ti = live_idx_of(m, t, idx, ns, lost, &sl);
+        if (ti == ~0u || !live_bit(u, sl)) return;
+        if (atomicMax(&colour[ti], c) < c && atomicExch(&stamp[ti], round) != round) next[atomicAdd(&lc->next_n, 1u)] = ti;
+    });
+    if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+}
+
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_scc_seed(const u32* __restrict__ list, u32 n, const u32* __restrict__ colour,
+                                                            u32* comp) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g < n && colour[list[g]] == list[g]) comp[list[g]] = list[g];
+}
+
+// next takes the states of wl that have not joined (a subset of wl).
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_scc_join(M m, const u64* __restrict__ arena, TableView t,
+                                                            const u32* __restrict__ idx, const u32* u,
+                                                            const u32* __restrict__ colour, u32* comp, const u32* __restrict__ wl,
+                                                            u32 n, u32* __restrict__ next, LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool keep = false, join = false;
+    u32 i = 0;
+    if (g < n) {
+        i = wl[g];
+        if (live_load(&comp[i]) == ~0u) {
+            u64 s[M::W], me[M::MW];
+            load_state<M::W>(arena, i, s);
+            const u32 c = colour[i];
+            bool lost = false;
+            live_moving(m, s, me, [&](int, const u64* ns) {
+                if (join) return;
+                u64 sl;
+                const u32 ti = live_idx_of(m, t, idx, ns, lost, &sl);
+                if (ti == ~0u || !live_bit(u, sl)) return;
+                join = colour[ti] == c && live_load(&comp[ti]) != ~0u;
+            });
+            if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+            if (join) live_store(&comp[i], c);
+            keep = !join;
+        }
+    }
+    live_append(keep, i, next, &lc->next_n);
+    const u64 jm = __ballot(join);
+    if (jm && (int)(threadIdx.x & 63) == __builtin_ctzll(jm)) atomicAdd(&lc->joined, (u32)__popcll(jm));
+}
+
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_scc_leave(const u32* __restrict__ list, u32 n, const u64* __restrict__ slot_of,
+                                                             const u32* __restrict__ comp, u32* u) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g >= n || comp[list[g]] == ~0u) return;
+    const u64 sl = slot_of[list[g]];
+    atomicAnd(&u[sl >> 5], ~(1u << (sl & 31)));
+}
+
+// and_me (all ones before the launch), or_took and size (zero) are by root.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_comp_acc(M m, const u64* __restrict__ arena, TableView t,
+                                                            const u32* __restrict__ idx, const u32* __restrict__ comp,
+                                                            const u32* __restrict__ list, u32 n, u32* size, u64* and_me,
+                                                            u64* or_took, LiveWeakCounters* lc) {
+    constexpr int MW = M::MW;
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    u32 root = ~0u;
+    u64 me[MW], took[MW];
+#pragma unroll
+    for (int w = 0; w < MW; ++w) me[w] = ~0ull, took[w] = 0;
+    if (g < n) {
+        const u32 i = list[g];
+        root = comp[i];
+        if (root != ~0u) {
+            u64 s[M::W];
+            load_state<M::W>(arena, i, s);
+            bool lost = false;
+            live_moving(m, s, me, [&](int a, const u64* ns) {
+                const u32 ti = live_idx_of(m, t, idx, ns, lost);
+                if (ti != ~0u && comp[ti] == root) took[a >> 6] |= 1ull << (a & 63);
+            });
+            if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+        }
+    }
+    const u64 active = __ballot(root != ~0u);
+    if (!active) return;
+    const int leader = __builtin_ctzll(active);
+    const u32 first = lane_u32(root, (u32)leader);
+    if (!__ballot(root != ~0u && root != first)) {  // the wave's members share one component
+#pragma unroll
+        for (int w = 0; w < MW; ++w) {
+            u64 a = me[w], o = took[w];  // (a lane without a member holds the neutral values)
+#pragma unroll
+            for (int d = 32; d; d >>= 1) {
+                a &= (u64)__shfl_xor((unsigned long long)a, d, 64);
+                o |= (u64)__shfl_xor((unsigned long long)o, d, 64);
+            }
+            if ((int)(threadIdx.x & 63) == leader) {
+                atomicAnd((unsigned long long*)&and_me[(size_t)first * MW + w], (unsigned long long)a);
+                if (o) atomicOr((unsigned long long*)&or_took[(size_t)first * MW + w], (unsigned long long)o);
+            }
+        }
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&size[first], (u32)__popcll(active));
+    } else if (root != ~0u) {
+#pragma unroll
+        for (int w = 0; w < MW; ++w) {
+            atomicAnd((unsigned long long*)&and_me[(size_t)root * MW + w], (unsigned long long)me[w]);
+            if (took[w]) atomicOr((unsigned long long*)&or_took[(size_t)root * MW + w], (unsigned long long)took[w]);
+        }
+        atomicAdd(&size[root], 1u);
+    }
+}
+
+// list: the NP list. rank holds 0 for the sinks (live_index) and ~0 elsewhere. next takes the states of F_p'
+// without a rank.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_goal(const u32* __restrict__ list, u32 n, const u64* __restrict__ slot_of,
+                                                        const u32* alive, const u32* __restrict__ comp, const u32* __restrict__ size,
+                                                        const u64* __restrict__ and_me, const u64* __restrict__ or_took, u32* rank,
+                                                        u32* __restrict__ next, LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool todo = false, goal = false, is_comp = false, is_fair = false;
+    u32 i = 0;
+    if (g < n) {
+        i = list[g];
+        if (live_bit(alive, slot_of[i])) {
+            goal = rank[i] == 0;
+            const u32 root = comp[i];
+            if (!goal && root != ~0u && size[root] >= 2) {
+                const bool fair = live_fair_masks<M::MW>(&and_me[(size_t)root * M::MW], &or_took[(size_t)root * M::MW]);
+                is_comp = root == i;
+                is_fair = is_comp && fair;
+                if (fair) rank[i] = 0, goal = true;
+            }
+            todo = !goal;
+        }
+    }
+    live_append(todo, i, next, &lc->next_n);
+    const u64 gm = __ballot(goal), cm = __ballot(is_comp), fm = __ballot(is_fair);
+    if ((threadIdx.x & 63) == 0) {
+        if (gm) atomicAdd(&lc->goal, (u32)__popcll(gm));
+        if (cm) atomicAdd(&lc->comps, (u32)__popcll(cm));
+        if (fm) atomicAdd(&lc->fair_comps, (u32)__popcll(fm));
+    }
+}
+
+// One level: a listed state (rank ~0) with a moving successor of rank < round takes rank `round`; the
+// others go to next.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_reach(M m, const u64* __restrict__ arena, TableView t,
+                                                         const u32* __restrict__ idx, u32* rank, u32 round,
+                                                         const u32* __restrict__ wl, u32 n, u32* __restrict__ next,
+                                                         LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool keep = false, join = false;
+    u32 i = 0;
+    if (g < n) {
+        i = wl[g];
+        u64 s[M::W], me[M::MW];
+        load_state<M::W>(arena, i, s);
+        bool lost = false;
+        live_moving(m, s, me, [&](int, const u64* ns) {
+            if (join) return;
+            const u32 ti = live_idx_of(m, t, idx, ns, lost);
+            join = ti != ~0u && live_load(&rank[ti]) < round;
+        });
+        if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+        if (join) live_store(&rank[i], round);
+        keep = !join;
+    }
+    live_append(keep, i, next, &lc->next_n);
+    const u64 jm = __ballot(join);
+    if (jm && (int)(threadIdx.x & 63) == __builtin_ctzll(jm)) atomicAdd(&lc->joined, (u32)__popcll(jm));
+}
+
+// list: the NP list; out takes the members of the component `root`.
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_members(const u32* __restrict__ list, u32 n, const u32* __restrict__ comp, u32 root,
+                                                           u32* __restrict__ out, LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    const bool in = g < n && comp[list[g]] == root;
+    live_append(in, in ? list[g] : 0u, out, &lc->next_n);
+}
+
+// The target set of a loop segment inside the component `root` (members: its list): plan LIVE_PLAN_NOTME the
+// members with !me(., a); LIVE_PLAN_TAKE those with me(., a) whose a-step stays in the component;
+// LIVE_PLAN_HOME the state `home`. A target gets rank 0 (lc->joined counts them), every other member ~0
+// and a place in next.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_targets(M m, const u64* __restrict__ arena, TableView t,
+                                                           const u32* __restrict__ idx, const u32* __restrict__ comp, u32 root,
+                                                           int plan, int a, u32 home, const u32* __restrict__ members, u32 n,
+                                                           u32* rank, u32* __restrict__ next, LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool hit = false, keep = false;
+    u32 i = 0;
+    if (g < n) {
+        i = members[g];
+        if (plan == LIVE_PLAN_HOME) {
+            hit = i == home;
+        } else {
+            u64 s[M::W], me[M::MW];
+            load_state<M::W>(arena, i, s);
+            bool lost = false, stays = false;
+            live_moving(m, s, me, [&](int b, const u64* ns) {
+                if (b != a || plan != LIVE_PLAN_TAKE) return;
+                const u32 ti = live_idx_of(m, t, idx, ns, lost);
+                stays = ti != ~0u && comp[ti] == root;
+            });
+            if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+            const bool mv = me[a >> 6] >> (a & 63) & 1;
+            hit = plan == LIVE_PLAN_NOTME ? !mv : stays;
+        }
+        rank[i] = hit ? 0u : ~0u;
+        keep = !hit;
+    }
+    live_append(keep, i, next, &lc->next_n);
+    const u64 hm = __ballot(hit);
+    if (hm && (int)(threadIdx.x & 63) == __builtin_ctzll(hm)) atomicAdd(&lc->joined, (u32)__popcll(hm));
+}
+
+// The lowest i < k whose init state has a rank, into lc->first_init (~0 before the launch). One workgroup.
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_first_ranked(const u64* __restrict__ slot_of, const u32* __restrict__ idx,
+                                                                const u32* __restrict__ rank, u32 k, LiveWeakCounters* lc) {
+    for (u32 i = threadIdx.x; i < k; i += LIVE_BLOCK) {
+        const u32 j = idx[slot_of[k - 1 - i]];
+        if (j != ~0u && rank[j] != ~0u) atomicMin(&lc->first_init, i);
+    }
+}
+
+// One wave. out holds max_steps + 2 states: out[0] is the state to go on from, state k + 1 the one step k
+// reached. From a state of rank r > 0 the wave takes the lowest slot whose moving successor has a rank
+// below r; at rank 0 it takes slot `then` if that is >= 0 and stops (LIVE_DESCEND_DONE). After max_steps
+// steps it stops with LIVE_DESCEND_MORE and the host launches it again from the last state. all = 1 (a
+// loop segment): every state passed adds the slots it does not move on to lc->notme and every step its
+// slot to lc->taken; all = 0 (the stem): only the state of rank 0 adds to lc->notme.
+template <class M>
+__global__ void __launch_bounds__(64) live_descend(M m, TableView t, const u32* __restrict__ idx, const u32* __restrict__ rank,
+                                                   u64* out, u32 max_steps, int then, u32 all, LiveWeakCounters* lc) {
+    constexpr int W = M::W, MW = M::MW;
+    const u32 lane = threadIdx.x;
+    u64 cur[W], notme[MW], taken[MW];
+#pragma unroll
+    for (int w = 0; w < MW; ++w) notme[w] = taken[w] = 0;
+    load_state<W>(out, 0, cur);
+    u32 err = 0, k = 0, end = LIVE_DESCEND_MORE, ci = ~0u;
+    auto wave_me = [&](u64* me) {  // the lanes' shares of the me mask, joined
+#pragma unroll
+        for (int w = 0; w < MW; ++w)
+#pragma unroll
+            for (int d = 32; d; d >>= 1) me[w] |= (u64)__shfl_xor((unsigned long long)me[w], d, 64);
+    };
+    while (!err) {  // (every condition below is wave-uniform)
+        bool lost = false;
+        ci = live_idx_of(m, t, idx, cur, lost);
+        const u32 r = ci == ~0u ? ~0u : rank[ci];
+        if (lost || r == ~0u) {
+            err |= lost ? LIVE_ERR_LOOKUP : LIVE_ERR_STUCK;
+            break;
+        }
+        if (r && k >= max_steps) break;
+        u64 me[MW], nx[W];
+        const int a = live_descend_step(
+            m, cur, r,
+            [&](const u64* ns) {
+                const u32 ti = live_idx_of(m, t, idx, ns, lost);
+                return ti == ~0u ? ~0u : rank[ti];
+            },
+            me, nx, lane, 64u);
+        if (__ballot(lost)) {
+            err |= LIVE_ERR_LOOKUP;
+            break;
+        }
+        wave_me(me);
+        if (all || !r)
+#pragma unroll
+            for (int w = 0; w < MW; ++w) notme[w] |= ~me[w];
+        if (!r) {
+            end = LIVE_DESCEND_DONE;
+            if (then >= 0) {  // (every lane computes the same step)
+                if (!m.apply(cur, then, nx)) {
+                    err |= LIVE_ERR_STUCK;
+                    break;
+                }
+#pragma unroll
+                for (int x = 0; x < W; ++x) cur[x] = nx[x];
+                ++k;
+                if (lane == 0) store_state<W>(out, k, cur);
+                taken[then >> 6] |= 1ull << (then & 63);
+                ci = live_idx_of(m, t, idx, cur, lost);
+                if (lost || ci == ~0u) {
+                    err |= LIVE_ERR_LOOKUP;
+                    break;
+                }
+                live_moving(m, cur, me, [](int, const u64*) {}, lane, 64u);
+                wave_me(me);
+#pragma unroll
+                for (int w = 0; w < MW; ++w) notme[w] |= ~me[w];
+            }
+            break;
+        }
+        int best = a >= 0 ? a : 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+        if (best == 0x7fffffff) {
+            err |= LIVE_ERR_STUCK;
+            break;
+        }
+        const int winner = __builtin_ctzll(__ballot(a == best));
+#pragma unroll
+        for (int x = 0; x < W; ++x) cur[x] = (u64)__shfl((unsigned long long)nx[x], winner, 64);
+        ++k;
+        if (lane == 0) store_state<W>(out, k, cur);
+        if (all) taken[best >> 6] |= 1ull << (best & 63);
+    }
+    if (lane == 0) {
+        lc->steps = k;
+        lc->end = end;
+        lc->last_idx = ci;
+        if (err) atomicOr(&lc->err, err);
+#pragma unroll
+        for (int w = 0; w < MW; ++w) lc->notme[w] |= notme[w], lc->taken[w] |= taken[w];
+    }
+}
+
 }  // namespace sr

@@ -39,15 +39,53 @@
 // on every maximal path that does not stay forever in ONE state that has a successor other than
 // itself. It is NOT per-action weak fairness: a cycle through two or more distinct states still
 // refutes p, however unfair the run round it is; fair strongly connected components are not built
-// (DESIGN.md §10). The simulation checker's loop detection is not changed (a self-loop still closes
-// a lasso there), and what the plain mode refuses (plugins, partitions, symmetry,
-// target_state_count) this mode refuses too.
+// in THIS mode (weak fairness, below, builds them). The simulation checker's loop detection is not
+// changed (a self-loop still closes a lasso there), and what the plain mode refuses (plugins,
+// partitions, symmetry, target_state_count) this mode refuses too.
+//
+// WEAK FAIRNESS (opt-in: sr_opts.liveness = SR_LIVENESS_WEAK, `CheckerBuilder.weak_fairness()`). The terms
+// of the progress mode (succ', terminal', N_p, F_p') stay as defined.
+//   fairness class  an action SLOT: an action of 2pc, a thread's step. A model opts in with `static
+//                   constexpr bool FAIR_SLOTS = true` (models.hpp fair_slots_model): DGraph, LiveGraph,
+//                   TwoPhase (so TwoPhaseLive), SpinLock. Every other model is refused at spawn: where a
+//                   slot is a network position (the actor encodings, paxos, the registers) it names no
+//                   action. The refusals of the other modes apply unchanged.
+//   me(s, a)        "moving-enabled": slot a is in enabled(s), apply(s, a) succeeds and its result differs
+//                   from s (TLA's ENABLED <A>_v: a no-op step neither creates nor discharges an
+//                   obligation). Where live_moves_model<M> holds, `enabled_moves` gives the mask.
+//   G'              the graph on F_p' with the succ' edges that stay in F_p' (no self edge).
+//   fair component  a strongly connected component C of G' with two or more states such that for every
+//                   slot a < max_actions(): some s in C has !me(s, a), or some s in C has me(s, a) and
+//                   apply(s, a) in C.
+//   goal            the terminal' states of F_p' and the members of fair components;
+//   FairF           the states of F_p' from which goal is reachable in G'; rank(s) is the length of the
+//                   shortest such path (computed level by level, so it is unique).
+// p has a counterexample iff some init state is in FairF; no discovery means p holds on every maximal run
+// that is weakly fair to every slot. MAXIMAL components suffice: if a strongly connected S inside C meets
+// the condition, so does C, because both disjuncts ("some state has !me", "some state's a-step stays
+// inside") only become easier in a larger set, and C is strongly connected; so a fair run that stays in
+// N_p for ever exists iff a maximal component is fair, and no recursive decomposition is needed. STRONG
+// fairness is not monotone like this (a larger set may enable a slot that the smaller never enables)
+// and is out of scope. Weak fairness subsumes progress fairness: a run that stutters for ever at a state
+// with a moving slot is unfair to that slot.
+// The witness is deterministic. Start at the init state of lowest index in FairF. STEM: from s take the
+// lowest slot whose result t != s is in FairF with rank(t) < rank(s), until rank 0 at a state g. If g
+// is terminal' the witness ends there (end_kind 1 or 3, loop_start -1). Otherwise g lies in a fair
+// component C and a CLOSED WALK inside C from g follows; with cur = g, for the slots a = 0, 1, .. in
+// order: skip a if the loop so far discharges it (a state on the loop, g included, has !me(., a), or a
+// step of the loop took a); else, if some state of C has !me(., a), go from cur to the nearest such state
+// (ranks towards that target set inside C, lowest rank-decreasing slot); else go the same way to the
+// nearest s in C with apply(s, a) in C and take a. After the last slot go to g the same way. The path's
+// last state equals path[loop_start], loop_start the index of g, end_kind 2; the loop may pass a state
+// more than once, and loop_start still means "the state the last state repeats". Cost: at most
+// max_actions() + 1 rank fixpoints over C (reported as `segments`, not bounded).
 //
 // The per-state rule and the witness step are ONE function, live_step below, which the kernels
 // (kernels_live.hpp: live_trim, live_walk) and the host form (live_host, the sr_liveness_host entry
 // point) instantiate; they differ only in how "is this successor in the set" is answered (the alive
 // bitmap by visited-set slot on the device, a hash map on the host).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <unordered_map>
@@ -124,6 +162,97 @@ SR_HD int live_step(const M& m, const u64* s, Alive&& alive, u64* out, u32 first
             }
         return any ? LIVE_DEAD : self ? LIVE_STUTTER : LIVE_TERMINAL;
     }
+}
+
+// ---- weak fairness: the per-state pieces, shared by the kernels (kernels_live.hpp) and live_host_weak ----
+
+// The moving successors of s in slot order, among the enabled slots of rank first, first + stride, ..
+// (as live_step shares them): f(a, ns) for every slot a with me(s, a), ns = apply(s, a), and `me` the
+// mask of those slots. MOVES as in live_step.
+template <bool MOVES = true, class M, class F>
+SR_HD void live_moving(const M& m, const u64* s, u64* me, F&& f, u32 first = 0, u32 stride = 1) {
+    u64 mask[M::MW], out[M::W];
+    if constexpr (MOVES && live_moves_model<M>) (void)m.enabled_moves(s, mask);
+    else m.enabled(s, mask);
+    u32 r = 0;
+    for (int w = 0; w < M::MW; ++w) {
+        me[w] = 0;
+        for (u64 bits = mask[w]; bits; bits &= bits - 1, ++r) {
+            if ((r & (stride - 1)) != first) continue;
+            const int b = __builtin_ctzll(bits);
+            if (!m.apply(s, w * 64 + b, out)) continue;
+            if constexpr (!(MOVES && live_moves_model<M>)) {
+                if (live_same<M::W>(out, s)) continue;
+            }
+            me[w] |= 1ull << b;
+            f(w * 64 + b, out);
+        }
+    }
+}
+
+// The fairness predicate of a component from its two accumulators: and_me, the AND over its members of
+// their me masks; or_took, the OR over its members of the slots whose successor is a member.
+template <int MW>
+SR_HD bool live_fair_masks(const u64* and_me, const u64* or_took) {
+    bool fair = true;
+#pragma unroll
+    for (int w = 0; w < MW; ++w) fair = fair && (and_me[w] & ~or_took[w]) == 0;
+    return fair;
+}
+
+// The witness' step choice: the lowest slot (of this call's share) whose moving successor has a rank
+// below `below`, with the successor in out; -1 if none. rank_of(ns) is the successor's rank in the
+// current domain (~0u outside it) and is asked in slot order up to the first hit; `me` is the mask
+// of this call's share of the moving slots, all of them.
+template <bool MOVES = true, class M, class Rank>
+SR_HD int live_descend_step(const M& m, const u64* s, u32 below, Rank&& rank_of, u64* me, u64* out, u32 first = 0,
+                            u32 stride = 1) {
+    int best = -1;
+    live_moving<MOVES>(
+        m, s, me,
+        [&](int a, const u64* ns) {
+            if (best >= 0 || !below || !(rank_of(ns) < below)) return;
+            best = a;
+#pragma unroll
+            for (int i = 0; i < M::W; ++i) out[i] = ns[i];
+        },
+        first, stride);
+    return best;
+}
+
+// What the closed walk does about slot a, given the loop so far (notme: slots not moving-enabled at some
+// state of it; taken: slots its steps took) and the component's and_me accumulator.
+enum LivePlan : int { LIVE_PLAN_SKIP = 0, LIVE_PLAN_NOTME = 1, LIVE_PLAN_TAKE = 2, LIVE_PLAN_HOME = 3 };
+inline int live_loop_plan(int a, const u64* notme, const u64* taken, const u64* and_me) {
+    const u64 bit = 1ull << (a & 63);
+    if ((notme[a >> 6] | taken[a >> 6]) & bit) return LIVE_PLAN_SKIP;
+    return and_me[a >> 6] & bit ? LIVE_PLAN_TAKE : LIVE_PLAN_NOTME;
+}
+
+// Whether the closed walk states[0 .. len] (W words each; states[len] equals states[0]) is weakly fair,
+// on its own states and steps: every slot below max_actions() is not moving-enabled at some state of
+// it, or some step i goes to that slot's successor of state i.
+template <class M>
+bool live_loop_fair(const M& m, const u64* states, size_t len) {
+    constexpr int W = M::W;
+    if (!len || !std::equal(states, states + W, states + len * W)) return false;
+    u64 notme[M::MW] = {}, taken[M::MW] = {}, me[M::MW];
+    for (size_t i = 0; i < len; ++i) {
+        live_moving<false>(m, states + i * W, me, [&](int a, const u64* ns) {
+            if (std::equal(ns, ns + W, states + (i + 1) * W)) taken[a >> 6] |= 1ull << (a & 63);
+        });
+        for (int w = 0; w < M::MW; ++w) notme[w] |= ~me[w];
+    }
+    for (int a = 0; a < m.max_actions(); ++a)
+        if (!((notme[a >> 6] | taken[a >> 6]) >> (a & 63) & 1)) return false;
+    return true;
+}
+
+inline sr_live_weak live_weak_none() {
+    sr_live_weak w;
+    std::memset(&w, 0, sizeof(w));
+    w.stem_len = w.loop_len = -1;
+    return w;
 }
 
 inline sr_live_result live_result_none() {
@@ -247,6 +376,295 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
     }
     h.r.pass_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return h;
+}
+
+// The check under WEAK FAIRNESS on the host, with no device, by other algorithms than the device's:
+// the host search and the progress fixpoint as live_host runs them, then Tarjan's algorithm
+// (iterative) for the components of G', breadth-first ranks over predecessor lists, and the witness
+// rule of the header. The per-state pieces (live_moving, live_fair_masks, live_descend_step,
+// live_loop_plan) are the kernels'.
+struct LiveHostWeak {
+    LiveHost h;
+    sr_live_weak w = live_weak_none();
+};
+
+template <bool MOVES = true, class M>
+LiveHostWeak live_host_weak(const M& m, int p, u64 max_states) {
+    constexpr int W = M::W, MW = M::MW;
+    constexpr u32 NONE = ~0u;
+    if constexpr (!fair_slots_model<M>) {
+        throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
+    } else {
+        if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
+            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
+        struct H {
+            size_t operator()(const std::vector<u64>& v) const {
+                u64 h = 0;
+                for (u64 x : v) h = fmix64(h ^ x) + 0x9E3779B97F4A7C15ull;
+                return (size_t)h;
+            }
+        };
+        const auto t0 = std::chrono::steady_clock::now();
+        std::unordered_map<std::vector<u64>, u32, H> index;
+        std::vector<std::vector<u64>> st;
+        auto add = [&](const u64* s) {
+            std::vector<u64> v(s, s + W);
+            auto it = index.find(v);
+            if (it != index.end()) return it->second;
+            if (st.size() >= max_states)
+                throw Error(SR_ERR_CAPACITY, "liveness: the model has more than " + std::to_string(max_states) + " reachable states (max_states)");
+            const u32 i = (u32)st.size();
+            index.emplace(v, i);
+            st.push_back(std::move(v));
+            return i;
+        };
+        const std::vector<u64> inits = init_states_of(m);
+        const int k = (int)(inits.size() / W);
+        std::vector<u32> init_idx;
+        for (int i = 0; i < k; ++i) init_idx.push_back(add(&inits[(size_t)i * W]));
+        for (size_t q = 0; q < st.size(); ++q) {
+            const std::vector<u64> s = st[q];  // (a copy: add() grows st)
+            for_each_successor(m, s.data(), [&](int, const u64* ns) { add(ns); });
+        }
+        LiveHostWeak res;
+        LiveHost& h = res.h;
+        sr_live_weak& wk = res.w;
+        h.unique = st.size();
+        h.r.ran = wk.ran = 1;
+        auto find = [&](const u64* ns) {
+            auto it = index.find(std::vector<u64>(ns, ns + W));
+            if (it == index.end()) throw Error(SR_ERR_NONDETERMINISM, "liveness: a successor of a reachable state is not in the reachable set");
+            return it->second;
+        };
+        // the progress fixpoint, as live_host<true> runs it
+        std::vector<char> alive(st.size(), 0);
+        {
+            std::vector<u32> wl, next;
+            for (u32 i = 0; i < (u32)st.size(); ++i)
+                if (live_not_p(m, p, st[i].data())) alive[i] = 1, wl.push_back(i);
+            h.r.not_p_states = h.r.surviving = wl.size();
+            auto is_alive = [&](const u64* ns) { return alive[find(ns)] != 0; };
+            u64 out[W];
+            for (;;) {
+                u64 removed = 0;
+                next.clear();
+                h.r.rounds += 1;
+                h.r.examined += wl.size();
+                for (u32 i : wl) {
+                    const int a = live_step<true, MOVES>(m, st[i].data(), is_alive, out);
+                    if (a >= 0) next.push_back(i);
+                    else if (a == LIVE_DEAD) alive[i] = 0, ++removed;
+                }
+                wl.swap(next);
+                h.r.surviving -= removed;
+                if (!removed) break;
+            }
+        }
+        const auto t1 = std::chrono::steady_clock::now();
+        // G': the states of F_p' (numbered by `pos`), their edges to other states of F_p', predecessors
+        std::vector<u32> fs, pos(st.size(), NONE);
+        for (u32 i = 0; i < (u32)st.size(); ++i)
+            if (alive[i]) pos[i] = (u32)fs.size(), fs.push_back(i);
+        const u32 nf = (u32)fs.size();
+        struct Edge {
+            u32 a, t;
+        };
+        std::vector<std::vector<Edge>> out_e(nf);
+        std::vector<std::vector<u32>> preds(nf);
+        std::vector<u64> me((size_t)nf * MW);
+        std::vector<char> sink(nf, 0);
+        for (u32 v = 0; v < nf; ++v) {
+            live_moving<MOVES>(m, st[fs[v]].data(), &me[(size_t)v * MW], [&](int a, const u64* ns) {
+                const u32 t = pos[find(ns)];
+                if (t != NONE) out_e[v].push_back({(u32)a, t}), preds[t].push_back(v);
+            });
+            bool any = false;
+            for (int w = 0; w < MW; ++w) any = any || me[(size_t)v * MW + w];
+            sink[v] = !any;
+        }
+        // |U|: F_p' without its sinks, trimmed to the states with a successor in it
+        {
+            std::vector<char> in_u(nf);
+            std::vector<u32> cnt(nf, 0), todo;
+            for (u32 v = 0; v < nf; ++v) in_u[v] = !sink[v];
+            for (u32 v = 0; v < nf; ++v) {
+                for (const Edge& e : out_e[v]) cnt[v] += in_u[e.t];
+                if (in_u[v] && !cnt[v]) todo.push_back(v);
+            }
+            while (!todo.empty()) {
+                const u32 v = todo.back();
+                todo.pop_back();
+                in_u[v] = 0;
+                for (u32 q : preds[v])
+                    if (in_u[q] && --cnt[q] == 0) todo.push_back(q);
+            }
+            for (u32 v = 0; v < nf; ++v) wk.cyclic_states += in_u[v];
+        }
+        // Tarjan, iterative: comp[v] = the component's number for a component of two or more states
+        std::vector<u32> comp(nf, NONE);
+        std::vector<std::vector<u32>> members;
+        {
+            std::vector<u32> num(nf, NONE), low(nf, 0), stack, at(nf, 0);
+            std::vector<char> on(nf, 0);
+            std::vector<u32> call;
+            u32 counter = 0;
+            for (u32 root = 0; root < nf; ++root) {
+                if (num[root] != NONE) continue;
+                call.push_back(root);
+                while (!call.empty()) {
+                    const u32 v = call.back();
+                    if (num[v] == NONE) num[v] = low[v] = counter++, stack.push_back(v), on[v] = 1;
+                    bool down = false;
+                    while (at[v] < out_e[v].size()) {
+                        const u32 t = out_e[v][at[v]].t;
+                        if (num[t] == NONE) {
+                            call.push_back(t);
+                            down = true;
+                            break;
+                        }
+                        if (on[t]) low[v] = std::min(low[v], num[t]);
+                        ++at[v];
+                    }
+                    if (down) continue;
+                    call.pop_back();
+                    if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[v]);
+                    if (low[v] == num[v]) {
+                        std::vector<u32> c;
+                        for (;;) {
+                            const u32 x = stack.back();
+                            stack.pop_back();
+                            on[x] = 0;
+                            c.push_back(x);
+                            if (x == v) break;
+                        }
+                        if (c.size() >= 2) {
+                            for (u32 x : c) comp[x] = (u32)members.size();
+                            members.push_back(std::move(c));
+                        }
+                    }
+                }
+            }
+        }
+        wk.components = members.size();
+        std::vector<u64> and_me(members.size() * MW, ~0ull), or_took(members.size() * MW, 0);
+        for (u32 v = 0; v < nf; ++v) {
+            if (comp[v] == NONE) continue;
+            for (int w = 0; w < MW; ++w) and_me[(size_t)comp[v] * MW + w] &= me[(size_t)v * MW + w];
+            for (const Edge& e : out_e[v])
+                if (comp[e.t] == comp[v]) or_took[(size_t)comp[v] * MW + (e.a >> 6)] |= 1ull << (e.a & 63);
+        }
+        std::vector<char> fair(members.size(), 0);
+        for (size_t c = 0; c < members.size(); ++c) {
+            fair[c] = live_fair_masks<MW>(&and_me[c * MW], &or_took[c * MW]);
+            wk.fair_components += fair[c];
+        }
+        // breadth-first ranks towards `targets` over the predecessors inside a domain (dom(v))
+        auto ranks_to = [&](const std::vector<u32>& targets, auto&& dom, std::vector<u32>& rank) -> u32 {
+            std::vector<u32> level = targets, nxt;
+            for (u32 v : targets) rank[v] = 0;
+            u32 rounds = 0;
+            for (u32 r = 1; !level.empty(); ++r, ++rounds) {
+                nxt.clear();
+                for (u32 t : level)
+                    for (u32 q : preds[t])
+                        if (dom(q) && rank[q] == NONE) rank[q] = r, nxt.push_back(q);
+                level.swap(nxt);
+            }
+            return rounds;
+        };
+        std::vector<u32> rank(nf, NONE), goal;
+        for (u32 v = 0; v < nf; ++v)
+            if (sink[v] || (comp[v] != NONE && fair[comp[v]])) goal.push_back(v);
+        wk.goal_states = goal.size();
+        wk.reach_rounds += ranks_to(goal, [](u32) { return true; }, rank);
+        for (u32 v = 0; v < nf; ++v) wk.fair_states += rank[v] != NONE;
+        for (int i = 0; i < k && h.r.init_index < 0; ++i)
+            if (alive[init_idx[i]] && rank[pos[init_idx[i]]] != NONE) h.r.init_index = i;
+        if (h.r.init_index >= 0) {
+            u64 notme[MW] = {}, taken[MW] = {};
+            u32 cur = pos[init_idx[h.r.init_index]];
+            h.words.assign(st[fs[cur]].begin(), st[fs[cur]].end());
+            // follows the lowest rank-decreasing slot from cur to rank 0, then takes slot `then` (if >= 0)
+            auto walk = [&](const std::vector<u32>& rk, int then, bool all) {
+                u64 mk[MW], nx[W];
+                auto step_to = [&](int a) {
+                    h.actions.push_back(m.action_id(st[fs[cur]].data(), a));
+                    cur = pos[find(nx)];
+                    if (cur == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness leaves F_p'");
+                    h.words.insert(h.words.end(), nx, nx + W);
+                };
+                for (;;) {
+                    const u32 r = rk[cur];
+                    if (r == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is at a state without a rank");
+                    const int a = live_descend_step<MOVES>(
+                        m, st[fs[cur]].data(), r,
+                        [&](const u64* ns) {
+                            const u32 t = pos[find(ns)];
+                            return t == NONE ? NONE : rk[t];
+                        },
+                        mk, nx);
+                    if (all || !r)
+                        for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
+                    if (!r) break;
+                    if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state has no successor of a lower rank");
+                    if (all) taken[a >> 6] |= 1ull << (a & 63);
+                    step_to(a);
+                }
+                if (then >= 0) {
+                    if (!m.apply(st[fs[cur]].data(), then, nx)) throw Error(SR_ERR_NONDETERMINISM, "liveness: the slot to take is refused");
+                    taken[then >> 6] |= 1ull << (then & 63);
+                    step_to(then);
+                    live_moving<MOVES>(m, st[fs[cur]].data(), mk, [](int, const u64*) {});
+                    for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
+                }
+            };
+            walk(rank, -1, false);
+            wk.stem_len = (int64_t)h.actions.size();
+            const u32 g = cur;
+            if (sink[g]) {
+                u64 all = 0;
+                for_each_successor(m, st[fs[g]].data(), [&](int, const u64*) { ++all; });
+                h.r.end_kind = all ? SR_LIVE_END_STUTTER : SR_LIVE_END_TERMINAL;
+                wk.loop_len = 0;
+            } else {
+                const u32 c = comp[g];
+                if (c == NONE || !fair[c]) throw Error(SR_ERR_NONDETERMINISM, "liveness: the stem ends outside every fair component");
+                std::vector<u32> lrank(nf, NONE), targets;
+                auto in_c = [&](u32 v) { return comp[v] == c; };
+                auto segment = [&](int then) {
+                    for (u32 v : members[c]) lrank[v] = NONE;
+                    wk.reach_rounds += ranks_to(targets, in_c, lrank);
+                    wk.segments += 1;
+                    walk(lrank, then, true);
+                };
+                for (int a = 0; a < m.max_actions(); ++a) {
+                    const int plan = live_loop_plan(a, notme, taken, &and_me[(size_t)c * MW]);
+                    if (plan == LIVE_PLAN_SKIP) continue;
+                    targets.clear();
+                    for (u32 v : members[c]) {
+                        const bool mv = me[(size_t)v * MW + (a >> 6)] >> (a & 63) & 1;
+                        bool hit = plan == LIVE_PLAN_NOTME && !mv;
+                        if (plan == LIVE_PLAN_TAKE && mv)
+                            for (const Edge& e : out_e[v]) hit = hit || ((int)e.a == a && comp[e.t] == c);
+                        if (hit) targets.push_back(v);
+                    }
+                    segment(plan == LIVE_PLAN_TAKE ? a : -1);
+                }
+                targets.assign(1, g);
+                segment(-1);
+                h.r.end_kind = SR_LIVE_END_LOOP;
+                h.r.loop_start = wk.stem_len;
+                wk.loop_len = (int64_t)h.actions.size() - wk.stem_len;
+                if (!live_loop_fair(m, &h.words[(size_t)wk.stem_len * W], (size_t)wk.loop_len))
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness is not weakly fair");
+            }
+            h.r.witness_len = (int64_t)h.actions.size();
+        }
+        const auto t2 = std::chrono::steady_clock::now();
+        h.r.pass_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
+        wk.pass_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+        return res;
+    }
 }
 
 }  // namespace sr

@@ -499,6 +499,8 @@ struct TwoPhaseT {
     // No slot that enabled_moves (or enabled & ~self_loops) leaves returns the state itself: see
     // self_loops above (sr_selftest_action_masks checks it over reachable and random states).
     static constexpr bool SELF_LOOPS_EXACT = true;
+    // A slot is an action of the protocol (TmCommit, RmPrepare(rm), ..): a fairness class (live.hpp, weak fairness).
+    static constexpr bool FAIR_SLOTS = true;
     // Six fields of a word to stride 5 (field i to bit 5i), three shift-and-mask steps like
     // working()'s compression: 2-bit fields at stride 2 (bits 0..11), 1-bit fields at stride 1.
     SR_HD static u32 spread2to5(u32 x) {
@@ -989,15 +991,19 @@ struct IncrementLock {
 // (1 <= roots <= 512). An optional seventh parameter, words = 1 (the default), 2 or 4, widens the state:
 // word i >= 1 holds fmix64(v + an odd constant of i), so every word is loaded, stored, shuffled and
 // compared (equal v <=> equal words), while the graph, the key and the description stay those of v.
+// An optional eighth parameter dup (default 0, dup <= roots, roots + dup <= 512) repeats the init states
+// 0 .. dup-1 after the roots, as Spread's does: duplicates that the search counts, queues and expands again.
 // -----------------------------------------------------------------------------------------------
 template <int W_>
 struct LiveGraphT {
     static_assert(W_ == 1 || W_ == 2 || W_ == 4, "LiveGraph: 1, 2 or 4 words");
     static constexpr int W = W_, MW = 1, NPROPS = 1;
+    static constexpr bool FAIR_SLOTS = true;  // edge k of every state is one fairness class (live.hpp, weak fairness)
     int n_bits, degree;
     u64 seed;
     u32 p_mod, t_mod;
     int roots;
+    int dup = 0;
     SR_HD u64 r(u64 v, u64 k) const { return fmix64(fmix64(seed ^ v) + k); }
     int max_actions() const { return degree; }
     int max_out_degree() const { return degree; }
@@ -1013,10 +1019,10 @@ struct LiveGraphT {
         return true;
     }
     SR_HD bool discovers(int, const u64* s) const { return p_mod && r(s[0], (u64)degree + 1) % p_mod == 0; }  // the condition holds
-    int init_count() const { return roots; }
+    int init_count() const { return roots + dup; }
     int init_states(u64* out) const {
-        for (int i = 0; i < roots; ++i) pack((u64)i, out + i * W_);
-        return roots;
+        for (int i = 0; i < roots + dup; ++i) pack((u64)(i < roots ? i : i - roots), out + i * W_);
+        return roots + dup;
     }
     int expectation(int) const { return EVENTUALLY; }
     const char* prop_name(int) const { return "marked"; }
@@ -1030,5 +1036,81 @@ struct LiveGraphT {
     std::string action_name(i64 id) const { return "Edge(" + std::to_string(id) + ")"; }
 };
 using LiveGraph = LiveGraphT<1>;
+
+// -----------------------------------------------------------------------------------------------
+// SpinLock(n): n threads take a lock in turn while a clock ticks (no reference counterpart; the
+// model of the complete `eventually` check's weak-fairness mode, live.hpp). One word, and the
+// packed key is the word. The key is DECLARED 8 bits wider than the word, as LiveGraph's is: (n + 1)
+// 2^(n+1) of the word's 2^(n+6) values are reachable, and a table with as many slots as a dense key
+// space has values homes every key in its first half (kernels.hpp make_table_view), which from
+// n = 16 on has fewer slots than the model has states; the spare bits keep the hashed keys sparse.
+//   [0,5)      holder  0 = free, i + 1 = thread i holds the lock (n <= 20)
+//   [5,5+n)    served  bit i: thread i has released the lock at least once
+//   5+n        tick
+// Slot i < n is Acquire(i), enabled iff the lock is free; slot n + i is Release(i), enabled iff
+// thread i holds it: it sets served bit i and frees the lock; slot 2n is Tick, always enabled,
+// flipping tick. No slot is a no-op, and a slot is a fairness class (FAIR_SLOTS): a thread's
+// acquire, a thread's release, the clock. (n + 1) 2^n 2 states, one init state (all zero).
+//   0  eventually "some thread served":  refuted with no fairness and under progress fairness by
+//      the two-state Tick cycle; holds under weak fairness (Acquire(i) stays moving-enabled round
+//      that cycle and is never taken)
+//   1  eventually "every thread served": refuted under weak fairness too, by a starvation lasso:
+//      Acquire(1) is disabled whenever thread 0 holds the lock, so weak fairness does not protect
+//      thread 1 (strong fairness would)
+// -----------------------------------------------------------------------------------------------
+struct SpinLock {
+    static constexpr int W = 1, MW = 1, NPROPS = 2;
+    static constexpr bool FAIR_SLOTS = true;
+    static constexpr bool SELF_LOOPS_EXACT = true;  // every enabled slot changes the state
+    int n;
+    int max_actions() const { return 2 * n + 1; }
+    int max_out_degree() const { return n + 1; }
+    u32 emask() const { return 3u; }
+    SR_HD u64 served_mask() const { return ((1ull << n) - 1) << 5; }
+    SR_HD void enabled(const u64* sp, u64* m) const {
+        const u32 holder = (u32)(sp[0] & 31);
+        m[0] = (holder ? 1ull << (n + holder - 1) : (1ull << n) - 1) | 1ull << (2 * n);
+    }
+    SR_HD bool apply(const u64* sp, int a, u64* o) const {
+        const u64 s = sp[0];
+        if (a < n) o[0] = s | (u64)(a + 1);                               // (enabled: holder == 0)
+        else if (a < 2 * n) o[0] = (s & ~31ull) | 1ull << (5 + a - n);     // (enabled: holder == a - n + 1)
+        else o[0] = s ^ 1ull << (5 + n);
+        return true;
+    }
+    SR_HD bool discovers(int p, const u64* sp) const {  // the condition holds
+        const u64 sv = sp[0] & served_mask();
+        return p == 0 ? sv != 0 : sv == served_mask();
+    }
+    int init_states(u64* out) const { out[0] = 0; return 1; }
+    int expectation(int) const { return EVENTUALLY; }
+    const char* prop_name(int p) const { return p == 0 ? "some thread served" : "every thread served"; }
+    int qkey_bits() const { return 14 + n; }
+    SR_HD unsigned __int128 qkey(const u64* s) const { return s[0]; }
+    int describe_width() const { return 3; }
+    void describe(const u64* s, i64* d) const {
+        d[0] = (i64)(s[0] & 31);
+        d[1] = (i64)((s[0] & served_mask()) >> 5);
+        d[2] = (i64)(s[0] >> (5 + n) & 1);
+    }
+    void undescribe(const i64* d, u64* s) const { s[0] = ((u64)d[0] & 31) | (u64)d[1] << 5 | ((u64)d[2] & 1) << (5 + n); }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return 2 * n + 1; }
+    std::string action_name(i64 id) const {
+        if (id == 2 * n) return "Tick";
+        return std::string(id < n ? "Acquire(" : "Release(") + std::to_string(id < n ? id : id - n) + ")";
+    }
+};
+
+// Models whose action slots are fairness classes (`static constexpr bool FAIR_SLOTS = true`): the
+// complete `eventually` check's weak-fairness mode (live.hpp) treats every slot as one action that
+// a fair run may not ignore for ever. Where a slot is a network position or a queue entry (the actor
+// encodings, paxos, the registers) it names no action of the model, and the mode is refused.
+template <class M, class = void>
+struct fair_slots : std::false_type {};
+template <class M>
+struct fair_slots<M, std::void_t<decltype(M::FAIR_SLOTS)>> : std::integral_constant<bool, M::FAIR_SLOTS> {};
+template <class M>
+constexpr bool fair_slots_model = fair_slots<M>::value && !is_canon<M>::value && !is_evbits<M>::value;
 
 }  // namespace sr

@@ -55,6 +55,16 @@ std::unique_ptr<EngineBase> reg_registers(const EngineArgs& a);       // ABD (8 
 std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16 and 32 network slots (W = 14, 22)
 std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4), LiveGraph
 std::unique_ptr<EngineBase> reg_two_phase_live(const EngineArgs& a);  // 2pc with `eventually` properties (TwoPhaseLive)
+std::unique_ptr<EngineBase> reg_spin_lock(const EngineArgs& a);       // SpinLock
+
+// SpinLock (models.hpp) of (threads), handed to f: the engine (reg_spin_lock.hip) and the host-only entry
+// points (engine.hip) validate alike.
+template <class F>
+auto with_spin_lock(const i64* p, int np, F&& f) {
+    if (np < 1) throw Error(SR_ERR_ARG, "spin-lock needs 1 param (threads)");
+    if (p[0] < 1 || p[0] > 20) throw Error(SR_ERR_UNSUPPORTED, "spin-lock: threads must be in 1..=20");
+    return f(SpinLock{(int)p[0]});
+}
 
 // TwoPhaseLive (models.hpp) of (rm_count), handed to f: the engines (reg_two_phase_live.hip) and the
 // host-only entry points (engine.hip) validate alike.
@@ -66,11 +76,11 @@ auto with_two_phase_live(const i64* p, int np, F&& f) {
 }
 
 // The LiveGraph fixture (models.hpp) of (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words
-// (default 1), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip)
+// (default 1) and dup (default 0), handed to f: the engines (reg_spread.hip) and the host-only entry points (engine.hip)
 // validate alike.
 template <class F>
 auto with_live_graph(const i64* p, int np, F&& f) {
-    if (np != 6 && np != 7) throw Error(SR_ERR_ARG, "live graph needs 6 params (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words");
+    if (np < 6 || np > 8) throw Error(SR_ERR_ARG, "live graph needs 6 params (n_bits, degree, seed, p_mod, t_mod, roots) and optionally words, dup");
     if (p[0] < 1 || p[0] > 24) throw Error(SR_ERR_UNSUPPORTED, "live graph: n_bits must be in 1..=24");
     if (p[1] < 1 || p[1] > 4) throw Error(SR_ERR_UNSUPPORTED, "live graph: degree must be in 1..=4");
     if (p[3] < 0 || p[3] > 0xffffffffll || p[4] < 0 || p[4] > 0xffffffffll)
@@ -78,9 +88,11 @@ auto with_live_graph(const i64* p, int np, F&& f) {
     if (p[5] < 1 || p[5] > 512 || p[5] > (i64)1 << p[0]) throw Error(SR_ERR_ARG, "live graph: roots must be in 1..=min(512, 2^n_bits)");
     const i64 w = np > 6 ? p[6] : 1;
     if (w != 1 && w != 2 && w != 4) throw Error(SR_ERR_UNSUPPORTED, "live graph: words must be 1, 2 or 4");
-    if (w == 1) return f(LiveGraphT<1>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
-    if (w == 2) return f(LiveGraphT<2>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
-    return f(LiveGraphT<4>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5]});
+    const i64 dup = np > 7 ? p[7] : 0;
+    if (dup < 0 || dup > p[5] || p[5] + dup > 512) throw Error(SR_ERR_ARG, "live graph: dup must be in 0..=roots, roots + dup at most 512");
+    if (w == 1) return f(LiveGraphT<1>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
+    if (w == 2) return f(LiveGraphT<2>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
+    return f(LiveGraphT<4>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
 }
 
 // The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark) and

@@ -58,6 +58,23 @@ class TwoPhaseLiveSys(_Model):
         return [self.rm_count]
 
 
+class SpinLockSys(_Model):
+    """`threads` threads take a lock in turn while a clock ticks (csrc/models.hpp `SpinLock`; no reference
+    counterpart), 1 <= threads <= 20: Acquire(i) while the lock is free, Release(i) by its holder (which
+    serves thread i), and Tick, always enabled. Two `eventually` properties: "some thread served", which
+    the Tick cycle refutes unless the check runs under `weak_fairness()`, and "every thread served", which
+    a starvation lasso refutes even then (it would take strong fairness)."""
+    MODEL_ID = N.SR_MODEL_SPIN_LOCK
+
+    def __init__(self, threads):
+        if not 1 <= threads <= 20:
+            raise ValueError("SpinLockSys: threads must be in 1..=20")
+        self.threads = threads
+
+    def params(self):
+        return [self.threads]
+
+
 class Increment(_Model):
     """`increment` example `State::new(n)` (examples/increment.rs:109-197)."""
     MODEL_ID = N.SR_MODEL_INCREMENT
@@ -233,12 +250,15 @@ class LiveGraph(_Model):
     holds at v iff p_mod > 0 and r(v, degree + 1) % p_mod == 0; the init states are 0 .. roots-1."""
     MODEL_ID = N.SR_MODEL_LIVE_GRAPH
 
-    def __init__(self, n_bits, degree, seed, p_mod, t_mod=0, roots=1, words=1):
+    def __init__(self, n_bits, degree, seed, p_mod, t_mod=0, roots=1, words=1, dup=0):
         self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots = n_bits, degree, seed, p_mod, t_mod, roots
         self.words = words  # 2 or 4: the same graph on states padded with words that are functions of v
+        self.dup = dup      # the init states 0 .. dup-1 once more after the roots (duplicates)
 
     def params(self):
         p = [self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots]
+        if self.dup:
+            return p + [self.words, self.dup]
         return p if self.words == 1 else p + [self.words]
 
 
