@@ -94,13 +94,23 @@ enum sr_model_id {
                                      has no terminal state (once Commit or Abort is sent, RmRcvCommitMsg /
                                      RmRcvAbortMsg stay enabled as self-loops), so it is the model of the complete
                                      `eventually` check's progress mode (SR_LIVENESS_PROGRESS) */
-    SR_MODEL_SPIN_LOCK = 17       /* (threads 1..20) n threads take a lock in turn while a clock ticks; one word:
+    SR_MODEL_SPIN_LOCK = 17,      /* (threads 1..20) n threads take a lock in turn while a clock ticks; one word:
                                      holder (0 free, i + 1) in bits [0,5), served (n bits) from bit 5, tick above.
                                      Slot i < n Acquire(i) (the lock is free), n + i Release(i) (thread i holds it:
                                      serves i and frees the lock), 2n Tick (always: flips tick); (n + 1) 2^n 2 states.
                                      Two `eventually` properties: 0 "some thread served", 1 "every thread served".
                                      No reference counterpart: the model of the complete `eventually` check's
                                      weak-fairness mode (SR_LIVENESS_WEAK) */
+    SR_MODEL_FAIR_RINGS = 18      /* (d 1..28, w 4..64, core 0..2, lanes 1..512) nested rings; one word: position x
+                                     in bits [0,6), ring k in [6,11), lane j in [11,20), done in bit 20. Lane j has
+                                     the rings 0 .. d_j, d_j = 1 + (j mod d); its core is on iff core == 1, or
+                                     core == 2 and j is odd. Slot 0 Step (x + 1 mod w); 1 + k Out(k), enabled at
+                                     (k, 0): to `done` for k = 0, else to (k - 1, 0), and with the core on and
+                                     k = d_j also at (k, 2), to (k, 0); d + 2 + k In(k), enabled at (k, 1) iff
+                                     k < d_j: to (k + 1, 1). One `eventually` property "done"; init states
+                                     (j, 0, 0). No reference counterpart and no oracle counterpart: the fixture of
+                                     the complete `eventually` check's strong-fairness mode (SR_LIVENESS_STRONG),
+                                     whose fair sets lie d_j levels deep inside unfair components */
 };
 
 /* Visit order inside a BFS level. */
@@ -111,14 +121,17 @@ enum sr_order {
 };
 
 /* sr_opts.liveness: the complete `eventually` check (see sr_gpu_bfs_liveness below). Every value but 0,
- * SR_LIVENESS_PROGRESS and SR_LIVENESS_WEAK is read as SR_LIVENESS_COMPLETE. */
+ * SR_LIVENESS_PROGRESS, SR_LIVENESS_WEAK and SR_LIVENESS_STRONG is read as SR_LIVENESS_COMPLETE. */
 enum sr_liveness_mode {
     SR_LIVENESS_OFF = 0,
     SR_LIVENESS_COMPLETE = 1, /* no fairness: a self-loop on a state where the property does not hold refutes it */
     SR_LIVENESS_PROGRESS = 2, /* progress fairness: a successor equal to its state is no successor */
-    SR_LIVENESS_WEAK = 3      /* weak fairness per action slot (see sr_gpu_bfs_liveness_weak below). Until this
+    SR_LIVENESS_WEAK = 3,     /* weak fairness per action slot (see sr_gpu_bfs_liveness_weak below). Until this
                                  value was given its meaning, 3 was one of the "other values" read as
-                                 SR_LIVENESS_COMPLETE; the values from 4 up still are */
+                                 SR_LIVENESS_COMPLETE */
+    SR_LIVENESS_STRONG = 4    /* strong fairness per action slot (see sr_gpu_bfs_liveness_strong below). Until
+                                 this value was given its meaning, 4 was one of the "other values" read as
+                                 SR_LIVENESS_COMPLETE; the values from 5 up still are */
 };
 /* sr_live_result.end_kind: how the witness ends (both modes). */
 enum sr_live_end { SR_LIVE_END_NONE = 0, SR_LIVE_END_TERMINAL = 1, SR_LIVE_END_LOOP = 2, SR_LIVE_END_STUTTER = 3 };
@@ -160,7 +173,7 @@ typedef struct sr_opts {
     int32_t reserved0;           /* what were 4 bytes of tail padding; never read                  */
     int32_t liveness;            /* 1 = the complete `eventually` check (see sr_gpu_bfs_liveness below); 2 = the
                                     same under progress fairness, 3 = under weak fairness per action
-                                    slot (enum sr_liveness_mode); 0 = off,
+                                    slot, 4 = under strong fairness (enum sr_liveness_mode); 0 = off,
                                     and then nothing changes. The struct grew from 56 to 64 bytes for it: a
                                     caller whose struct_size is 56 is read as liveness = 0, whatever its
                                     padding holds                                                   */
@@ -422,6 +435,55 @@ int64_t sr_liveness_host_weak(int32_t model_id, const int64_t* params, int32_t n
  * taken by one of its steps; 0: it is not, or the loop is not closed or has no step; -1: the actions
  * cannot be replayed, or the model's slots are not fairness classes. */
 int32_t sr_gpu_bfs_loop_fair(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n, int32_t loop_start);
+
+/* ---- STRONG FAIRNESS (liveness = SR_LIVENESS_STRONG = 4, off by default; live.hpp and DESIGN.md section 12
+ * have the definition) ----
+ * Slots, me(s, a), F_p', its sinks and its graph G' are those of the weak mode, and the same models take it
+ * (every other is refused at spawn with SR_ERR_UNSUPPORTED, as is everything the other modes refuse). A set S
+ * of two or more states of F_p', strongly connected in G'[S], is STRONGLY FAIR iff for every slot a no member
+ * has me(., a), or some member has me(., a) and its a-step stays in S. Such a set may lie inside a component
+ * that is not fair (a larger set may enable a slot the smaller never enables), so the components are
+ * DECOMPOSED: for a component C of G'[X], bad(C) is the set of slots that are moving-enabled somewhere in C
+ * and whose steps all leave C; with bad(C) empty, C is a FAIR NODE; otherwise the components of C without the
+ * states that enable a bad slot are decomposed in the same way, starting from X = F_p' at depth 1. goal = the
+ * sinks of F_p' and the members of fair nodes; FairF = the states of F_p' from which goal is reachable. The
+ * property has a counterexample iff an init state is in FairF; no discovery means it holds on every maximal
+ * run that is strongly fair to every slot (a slot moving-enabled again and again is taken again and again),
+ * which subsumes weak fairness. The witness is deterministic: the weak mode's stem; at a sink it ends
+ * (end_kind 1 or 3, loop_start -1); otherwise a closed walk inside the fair node follows, which takes, for the
+ * slots in order, every slot that some member moves on and no step of the loop so far took, from the nearest
+ * member whose step stays inside, and then goes home (end_kind 2, loop_start = stem_len). It is not the
+ * shortest counterexample. One GPU, registered models only; levels and rounds are reported, not bounded. */
+typedef struct sr_live_strong {
+    int32_t ran;              /* 1 = the pass ran for this property in this mode                      */
+    uint32_t levels;          /* depth of the decomposition tree; 0 without a component               */
+    uint64_t cyclic_states;   /* F_p' without its sinks, trimmed to the states with a successor in it  */
+    uint64_t components;      /* nodes of the tree: components of two or more states, at every depth   */
+    uint64_t fair_components; /* fair nodes (pairwise disjoint)                                        */
+    uint64_t goal_states;     /* sinks of F_p' and members of fair nodes                               */
+    uint64_t fair_states;     /* |FairF|                                                              */
+    int64_t stem_len;         /* steps from the init state to the sink or into the fair node; -1       */
+    int64_t loop_len;         /* steps of the closed walk; 0 where the witness ends at a sink; -1      */
+    uint32_t scc_rounds;      /* implementation details (kernel rounds of the component searches, of   */
+    uint32_t reach_rounds;    /* the rank fixpoints, and rank fixpoints run for the loop): never        */
+    uint32_t segments;        /* compare them                                                           */
+    uint32_t reserved1;
+    double pass_ms;           /* wall time of what this mode adds to the pass for this property        */
+} sr_live_strong;
+/* The strong-fairness figures for property `prop` of a joined check (ran = 0: the check ran in another mode,
+ * or sr_gpu_bfs_liveness would say ran = 0). */
+int32_t sr_gpu_bfs_liveness_strong(const sr_bfs* bfs, int32_t prop, sr_live_strong* out);
+/* Host-only (no device needed): sr_liveness_host under strong fairness, by other algorithms than the
+ * device's (the decomposition tree by recursion with Tarjan's components, breadth-first ranks over
+ * predecessor lists). SR_ERR_UNSUPPORTED for a model whose slots are not fairness classes. */
+int64_t sr_liveness_host_strong(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int64_t max_states,
+                                sr_live_result* out, sr_live_strong* strong, int64_t* action_ids, int32_t cap);
+/* Host-only: whether the loop of a lasso is strongly fair; replayed as sr_gpu_bfs_loop_fair replays it. 1:
+ * every slot that is moving-enabled at some state of the loop is taken by one of its steps; 0: it is not, or
+ * the loop is not closed or has no step; -1: the actions cannot be replayed, or the model's slots are not
+ * fairness classes. */
+int32_t sr_gpu_bfs_loop_strongly_fair(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n,
+                                      int32_t loop_start);
 /* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
  * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds
  * them. The dump is int64s: [states, init states, properties, the init states' numbers..., then per

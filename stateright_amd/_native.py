@@ -26,6 +26,7 @@ SR_MODEL_SPREAD = 14
 SR_MODEL_LIVE_GRAPH = 15
 SR_MODEL_2PC_LIVE = 16
 SR_MODEL_SPIN_LOCK = 17
+SR_MODEL_FAIR_RINGS = 18
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
 SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
@@ -53,7 +54,7 @@ class sr_opts(ctypes.Structure):
 
 
 # sr_opts.liveness (enum sr_liveness_mode) and sr_live_result.end_kind (enum sr_live_end)
-SR_LIVENESS_OFF, SR_LIVENESS_COMPLETE, SR_LIVENESS_PROGRESS, SR_LIVENESS_WEAK = 0, 1, 2, 3
+SR_LIVENESS_OFF, SR_LIVENESS_COMPLETE, SR_LIVENESS_PROGRESS, SR_LIVENESS_WEAK, SR_LIVENESS_STRONG = 0, 1, 2, 3, 4
 SR_LIVE_END_NONE, SR_LIVE_END_TERMINAL, SR_LIVE_END_LOOP, SR_LIVE_END_STUTTER = 0, 1, 2, 3
 
 
@@ -79,6 +80,28 @@ class sr_live_weak(ctypes.Structure):
     _fields_ = [
         ("ran", ctypes.c_int32),
         ("reserved0", ctypes.c_int32),
+        ("cyclic_states", ctypes.c_uint64),
+        ("components", ctypes.c_uint64),
+        ("fair_components", ctypes.c_uint64),
+        ("goal_states", ctypes.c_uint64),
+        ("fair_states", ctypes.c_uint64),
+        ("stem_len", ctypes.c_int64),
+        ("loop_len", ctypes.c_int64),
+        ("scc_rounds", ctypes.c_uint32),
+        ("reach_rounds", ctypes.c_uint32),
+        ("segments", ctypes.c_uint32),
+        ("reserved1", ctypes.c_uint32),
+        ("pass_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+class sr_live_strong(ctypes.Structure):
+    _fields_ = [
+        ("ran", ctypes.c_int32),
+        ("levels", ctypes.c_uint32),
         ("cyclic_states", ctypes.c_uint64),
         ("components", ctypes.c_uint64),
         ("fair_components", ctypes.c_uint64),
@@ -255,6 +278,10 @@ SIGNATURES = [
     ("sr_liveness_host_weak", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                ctypes.POINTER(sr_live_result), ctypes.POINTER(sr_live_weak), _I64P, ctypes.c_int32]),
     ("sr_gpu_bfs_loop_fair", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32]),
+    ("sr_gpu_bfs_liveness_strong", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(sr_live_strong)]),
+    ("sr_liveness_host_strong", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                 ctypes.POINTER(sr_live_result), ctypes.POINTER(sr_live_strong), _I64P, ctypes.c_int32]),
+    ("sr_gpu_bfs_loop_strongly_fair", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32]),
     ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
     ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
     ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -498,6 +525,32 @@ def liveness_host_weak(model_id, params, prop=0, max_states=1 << 22):
     out["unique"] = n
     out["actions"] = list(acts[:max(0, res.witness_len)])
     out["weak"] = weak.as_dict()
+    return out
+
+
+def liveness_host_strong(model_id, params, prop=0, max_states=1 << 22):
+    """The complete `eventually` check under strong fairness on the host (csrc/live.hpp live_host_strong; no
+    device needed): the dict of `liveness_host`, plus `strong`, the dict of sr_live_strong (levels,
+    cyclic_states, components, fair_components, goal_states, fair_states, stem_len, loop_len, ...). The
+    witness' `actions` are the stem's followed by the closed walk's; ValueError (status -4) for a model whose
+    slots are not fairness classes."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    res, strong = sr_live_result(), sr_live_strong()
+    cap = 1 << 16
+    while True:
+        acts = (ctypes.c_int64 * cap)()
+        n = lib.sr_liveness_host_strong(model_id, arr, len(params), prop, max_states, ctypes.byref(res), ctypes.byref(strong), acts, cap)
+        if n < 0:
+            raise ValueError(f"sr_liveness_host_strong: {last_error()} (status {n})")
+        if res.witness_len <= cap:
+            break
+        cap = res.witness_len
+    out = res.as_dict()
+    out["unique"] = n
+    out["actions"] = list(acts[:max(0, res.witness_len)])
+    out["strong"] = strong.as_dict()
     return out
 
 

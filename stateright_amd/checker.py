@@ -237,6 +237,24 @@ class CheckerBuilder:
         self._opts.liveness = N.SR_LIVENESS_WEAK if on else 0
         return self
 
+    def strong_fairness(self, on=True):
+        """Engine opt-in: the complete `eventually` check under STRONG FAIRNESS per action slot (DESIGN.md
+        section 12). Like `weak_fairness()`, and further: a slot that is moving-enabled again and again
+        must be taken again and again, also where it is disabled in between (a thread's acquire while
+        another thread holds the lock), so a starvation loop no longer refutes "every client is
+        eventually served". A cycle refutes an `eventually` property only if some strongly connected
+        set of its states takes, inside the set, every slot that a member moves on; such sets may lie
+        inside components that are not fair, so the components are decomposed level by level
+        (`liveness(name)["strong"]` has the figures: levels, components, fair_components, ...; there is
+        no "weak" key in this mode). A discovery made by the pass ends at a terminal state or a stutter
+        end, or is a lasso whose loop is strongly fair; `assert_discovery` accepts a lasso only if the
+        host model finds its loop strongly fair. No discovery means: the property holds on every
+        maximal run that is strongly fair to every slot, which subsumes weak fairness. The same models
+        take it as `weak_fairness()`, with the same refusals; one GPU, the witness is not the shortest,
+        and the number of levels is reported, not bounded. `on=False` turns the complete check off."""
+        self._opts.liveness = N.SR_LIVENESS_STRONG if on else 0
+        return self
+
     def verbose(self, on=True):
         self._opts.verbose = int(bool(on))
         return self
@@ -383,7 +401,8 @@ class GpuBfsChecker:
             self._h = lib.sr_gpu_bfs_spawn(model.MODEL_ID, arr, len(params), ctypes.byref(opts))
         self._liveness = bool(opts.liveness)
         self._weak = opts.liveness == N.SR_LIVENESS_WEAK
-        self._progress = opts.liveness == N.SR_LIVENESS_PROGRESS or self._weak  # (weak fairness subsumes it)
+        self._strong = opts.liveness == N.SR_LIVENESS_STRONG
+        self._progress = opts.liveness == N.SR_LIVENESS_PROGRESS or self._weak or self._strong  # (both subsume it)
         self._spawned("sr_gpu_bfs_spawn")
 
     def _spawned(self, what):
@@ -581,7 +600,10 @@ class GpuBfsChecker:
         property holds) and pass_ms. A check under `weak_fairness()` adds "weak": the dict of sr_live_weak
         (cyclic_states, components, fair_components, goal_states, fair_states, stem_len, loop_len, and the
         round counters, which are implementation details); `surviving` is then |F_p'|, and `loop_start`
-        the state the last state repeats (the closed walk may pass it more than once)."""
+        the state the last state repeats (the closed walk may pass it more than once). A check under
+        `strong_fairness()` adds "strong" instead: the dict of sr_live_strong (levels, the depth of the
+        decomposition tree, components, all its nodes, fair_components, its fair nodes, and the rest as
+        for "weak")."""
         r = N.sr_live_result()
         st = self._lib.sr_gpu_bfs_liveness(self._h, self._prop_index(name), ctypes.byref(r))
         if st != 0:
@@ -594,6 +616,13 @@ class GpuBfsChecker:
                 raise CheckerError("sr_gpu_bfs_liveness_weak", st)
             if w.ran:
                 out["weak"] = w.as_dict()
+        if getattr(self, "_strong", False) and r.ran:
+            g = N.sr_live_strong()
+            st = self._lib.sr_gpu_bfs_liveness_strong(self._h, self._prop_index(name), ctypes.byref(g))
+            if st != 0:
+                raise CheckerError("sr_gpu_bfs_liveness_strong", st)
+            if g.ran:
+                out["strong"] = g.as_dict()
         return out
 
     def loop_start(self, name):
@@ -698,11 +727,13 @@ class GpuBfsChecker:
         """Whether this check ran under progress fairness (`complete_liveness(fairness="progress")`)."""
         return getattr(self, "_progress", False)
 
-    def _loop_is_fair(self, actions, init, loop_start):
-        """The host model's answer for the loop of a lasso (sr_gpu_bfs_loop_fair): True iff it is weakly fair."""
+    def _loop_is_fair(self, actions, init, loop_start, strong=False):
+        """The host model's answer for the loop of a lasso (sr_gpu_bfs_loop_fair): True iff it is weakly fair;
+        strong: iff it is strongly fair (sr_gpu_bfs_loop_strongly_fair)."""
         ids = [self.action_id(a) for a in actions]
         arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
-        return self._lib.sr_gpu_bfs_loop_fair(self._h, init, arr, len(ids), loop_start) == 1
+        ask = self._lib.sr_gpu_bfs_loop_strongly_fair if strong else self._lib.sr_gpu_bfs_loop_fair
+        return ask(self._h, init, arr, len(ids), loop_start) == 1
 
     def _sink_kind(self, actions, init):
         """The host model's answer for the state the actions lead to from init state `init`: 0 it has a
@@ -720,7 +751,8 @@ class GpuBfsChecker:
         path: the cycle between them can repeat forever. A check under progress fairness also accepts,
         for an `eventually` property, a path that ends at a stutter end (a state with successors that
         all are the state itself), decided on the host model. A check under weak fairness accepts stutter
-        ends likewise, and a lasso only if its loop is weakly fair on the host model."""
+        ends likewise, and a lasso only if its loop is weakly fair on the host model; a check under strong
+        fairness likewise, and a lasso only if its loop is strongly fair there."""
         found = self.assert_any_discovery(name)
         i = self._prop_index(name)
         exp = self.properties()[i][1]
@@ -746,6 +778,10 @@ class GpuBfsChecker:
                         closed = self._loop_is_fair(actions, init, states.index(states[-1]))
                         if not closed:
                             info.append("incorrect counterexample closes a loop that is not weakly fair")
+                    if closed and getattr(self, "_strong", False):  # (strong fairness: only a strongly fair loop)
+                        closed = self._loop_is_fair(actions, init, states.index(states[-1]), strong=True)
+                        if not closed:
+                            info.append("incorrect counterexample closes a loop that is not strongly fair")
                 if not terminal and not closed and self._accepts_stutter_ends():
                     closed = self._sink_kind(actions, init) == N.SR_LIVE_END_STUTTER
                 if not satisfied and (terminal or closed):

@@ -44,6 +44,7 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
             return reg_spread(a);
         case SR_MODEL_2PC_LIVE: return reg_two_phase_live(a);
         case SR_MODEL_SPIN_LOCK: return reg_spin_lock(a);
+        case SR_MODEL_FAIR_RINGS: return reg_fair_rings(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
@@ -442,6 +443,8 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             return with_two_phase_live(p, np, [&](const auto& m) -> i64 { return f(m); });
         case SR_MODEL_SPIN_LOCK:
             return with_spin_lock(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_FAIR_RINGS:
+            return with_fair_rings(p, np, [&](const auto& m) -> i64 { return f(m); });
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -750,6 +753,52 @@ int64_t sr_liveness_host_weak(int32_t model, const int64_t* p, int32_t np, int32
             }
         });
         if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host_weak: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int32_t sr_gpu_bfs_liveness_strong(const sr_bfs* b, int32_t prop, sr_live_strong* out) {
+    if (!b || !out || !b->e->finished.load(std::memory_order_acquire) || !b->e->live_strong_result(prop, out)) return SR_ERR_ARG;
+    return SR_OK;
+}
+
+int32_t sr_gpu_bfs_loop_strongly_fair(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t loop_start) {
+    if (!b || !b->e->finished.load(std::memory_order_acquire) || n < 0 || (n > 0 && !ids) || loop_start < 0 || loop_start > n) return -1;
+    try {
+        return b->e->loop_fair(init, ids, n, loop_start, true);
+    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
+        set_error(x.what());
+        return -1;
+    }
+}
+
+int64_t sr_liveness_host_strong(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_live_result* out,
+                                sr_live_strong* strong, int64_t* action_ids, int32_t cap) {
+    try {
+        if (!out || !strong || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host_strong: out, strong and max_states >= 1");
+        const char* e = std::getenv("SR_LIVE_MOVES");  // (as in sr_liveness_host_fair)
+        const bool moves = !e || std::atoi(e) != 0;
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            if constexpr (has_emask<M>::value) {
+                const LiveHostStrong h = moves ? live_host_strong<true>(m, prop, (u64)max_states) : live_host_strong<false>(m, prop, (u64)max_states);
+                *out = h.h.r;
+                *strong = h.s;
+                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.h.actions.size(); ++i) action_ids[i] = h.h.actions[i];
+                return (i64)h.h.unique;
+            } else if constexpr (!fair_slots_model<M>) {
+                throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
+            } else {
+                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
+            }
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host_strong: model " + std::to_string(model) + " has no host form");
         return r;
     } catch (const Error& x) {
         set_error(x.what());

@@ -93,14 +93,21 @@ class EngineBase {
         return true;
     }
     // Whether the loop of the lasso that the actions describe from init state `init` is weakly fair
-    // (sr_gpu_bfs_loop_fair).
-    virtual int loop_fair(int init, const i64* ids, int n, int loop_start) const {
-        (void)init, (void)ids, (void)n, (void)loop_start;
+    // (sr_gpu_bfs_loop_fair); strong: strongly fair (sr_gpu_bfs_loop_strongly_fair).
+    virtual int loop_fair(int init, const i64* ids, int n, int loop_start, bool strong = false) const {
+        (void)init, (void)ids, (void)n, (void)loop_start, (void)strong;
         return -1;
+    }
+    // The strong-fairness figures of that check (sr_gpu_bfs_liveness_strong); false: p is no property.
+    bool live_strong_result(int p, sr_live_strong* out) const {
+        if (p < 0 || p >= nprops()) return false;
+        *out = p < (int)live_strong.size() ? live_strong[p] : live_strong_none();
+        return true;
     }
 
     std::vector<sr_live_result> live;  // per property (empty: the pass never ran)
     std::vector<sr_live_weak> live_weak;  // per property (empty: the pass never ran in the weak mode)
+    std::vector<sr_live_strong> live_strong;  // per property (empty: the pass never ran in the strong mode)
     std::atomic<u64> state_count{0}, unique{0};
     std::atomic<u32> max_depth{0};
     std::atomic<bool> finished{false};
@@ -156,9 +163,10 @@ int sink_kind_model(const M& m, int init, const i64* ids, int n) {
 
 // sr_gpu_bfs_loop_fair: the actions are replayed from init state `init` as sink_kind_model replays them;
 // the loop is the states from index loop_start to the last. -1 no such path (or the model's slots are
-// no fairness classes), 1 the loop is closed and weakly fair (live.hpp live_loop_fair), 0 it is not.
+// no fairness classes), 1 the loop is closed and weakly fair (live.hpp live_loop_fair; strong: strongly fair,
+// live_loop_strong_fair), 0 it is not.
 template <class M>
-int loop_fair_model(const M& m, int init, const i64* ids, int n, int loop_start) {
+int loop_fair_model(const M& m, int init, const i64* ids, int n, int loop_start, bool strong = false) {
     constexpr int W = M::W;
     if constexpr (!fair_slots_model<M>) {
         return -1;
@@ -176,7 +184,8 @@ int loop_fair_model(const M& m, int init, const i64* ids, int n, int loop_start)
             if (!found) return -1;
             path.insert(path.end(), nx.begin(), nx.end());
         }
-        return live_loop_fair(m, &path[(size_t)loop_start * W], (size_t)(n - loop_start)) ? 1 : 0;
+        const u64* loop = &path[(size_t)loop_start * W];
+        return (strong ? live_loop_strong_fair(m, loop, (size_t)(n - loop_start)) : live_loop_fair(m, loop, (size_t)(n - loop_start))) ? 1 : 0;
     }
 }
 
@@ -391,6 +400,8 @@ class Engine final : public EngineBase {
                 throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
             if (o_.liveness == SR_LIVENESS_WEAK && !(fair_slots_model<M> && M::MW <= LIVE_MW_MAX))
                 throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
+            if (o_.liveness == SR_LIVENESS_STRONG && !(fair_slots_model<M> && M::MW <= LIVE_MW_MAX))
+                throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
         }
         // Internal tuning knobs (not part of the ABI): successors per lane per probe round and
         // the visited-set load factor the capacity hint is sized for.
@@ -525,8 +536,8 @@ class Engine final : public EngineBase {
         return replay_model(base_model(m_), init, ids, n, states, conds, all_conds, terminal);
     }
     int sink_kind(int init, const i64* ids, int n) const override { return sink_kind_model(base_model(m_), init, ids, n); }
-    int loop_fair(int init, const i64* ids, int n, int loop_start) const override {
-        return loop_fair_model(base_model(m_), init, ids, n, loop_start);
+    int loop_fair(int init, const i64* ids, int n, int loop_start, bool strong) const override {
+        return loop_fair_model(base_model(m_), init, ids, n, loop_start, strong);
     }
     int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                 std::vector<i64>& states) const override {
@@ -977,6 +988,7 @@ class Engine final : public EngineBase {
         for (auto& d : disc) d = DiscoveryRec{};
         live.clear();
         live_weak.clear();
+        live_strong.clear();
         live_path_.assign(M::NPROPS, {});
         stats = sr_stats{};
         stats.words_per_state = W;
@@ -1405,10 +1417,12 @@ class Engine final : public EngineBase {
     // The arena is R, the final visited set names its states. Every buffer lives for this call only.
     // sr_opts.liveness = SR_LIVENESS_PROGRESS launches the FAIR instantiations of live_trim and
     // live_walk (progress fairness, live.hpp); SR_LIVENESS_WEAK launches the FAIR live_trim and then
-    // live_weak_pass below in place of the walk; every other value launches the plain ones.
+    // live_weak_pass below in place of the walk, SR_LIVENESS_STRONG likewise live_strong_pass; every other
+    // value launches the plain ones.
     void live_pass() {
         live.assign(M::NPROPS, live_result_none());
         live_weak.assign(M::NPROPS, live_weak_none());
+        live_strong.assign(M::NPROPS, live_strong_none());
         if constexpr (has_emask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
             u32 todo = 0;
             for (int p = 0; p < M::NPROPS; ++p)
@@ -1418,7 +1432,8 @@ class Engine final : public EngineBase {
                 throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
             const u32 n = (u32)lstart_.back();
             const bool weak = o_.liveness == SR_LIVENESS_WEAK;  // (refused at spawn unless fair_slots_model<M>)
-            const bool fair = o_.liveness == SR_LIVENESS_PROGRESS || weak;
+            const bool strong = o_.liveness == SR_LIVENESS_STRONG;  // (likewise)
+            const bool fair = o_.liveness == SR_LIVENESS_PROGRESS || weak || strong;
             const TableView t = view();
             const size_t bwords = (size_t)((cap_ + 31) / 32);
             DBuf<u64> slot_of, lcb, out;
@@ -1458,7 +1473,7 @@ class Engine final : public EngineBase {
                 r.not_p_states = r.surviving = cnt;
                 const u32 np_cnt = cnt;
                 int last = 0;  // the worklist the last round wrote: the states of the fixpoint that are no sinks
-                if (weak) {  // the weak mode keeps live_mark's list
+                if (weak || strong) {  // the weak and the strong mode keep live_mark's list
                     if (!np_list.p) np_list.alloc(o_.device, n);
                     SR_HIP(hipMemcpyAsync(np_list.p, wl[0].p, (size_t)np_cnt * sizeof(u32), hipMemcpyDeviceToDevice, stream_));
                 }
@@ -1487,6 +1502,12 @@ class Engine final : public EngineBase {
                 if (weak) {
                     live_weak_pass(p, r, live_weak[p], n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
                                    inits, k, walk_steps);
+                    r.pass_ms = secs(t0, Clock::now()) * 1e3;
+                    continue;
+                }
+                if (strong) {
+                    live_strong_pass(p, r, live_strong[p], n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
+                                     inits, k, walk_steps);
                     r.pass_ms = secs(t0, Clock::now()) * 1e3;
                     continue;
                 }
@@ -1786,11 +1807,248 @@ class Engine final : public EngineBase {
         }
     }
 
+    // STRONG FAIRNESS (live.hpp; the kernels' header in kernels_live.hpp), behind live_mark and the progress
+    // trim of property p, with the weak pass' arguments. The host form's recursive tree becomes level-synchronous
+    // rounds over all open components at once: W starts as the weak mode's U; a level takes the components of
+    // G'[W] (the weak mode's colour, seed, join and leave kernels over the W bitmap), accumulates or_me and
+    // or_took per component (live_comp_acc_or), lets live_refine freeze the fair nodes, drop the states that
+    // enable a bad slot and hand the rest back to W, and trims W again; until W is empty. One counter read-back
+    // per round. Memory is the weak pass' plus one list of 4 bytes per state of N_p (the level's members); no
+    // level stamp is kept per state, because live_refine clears the component number of every state that is
+    // not frozen.
+    void live_strong_pass(int p, sr_live_result& r, sr_live_strong& sg, u32 n, const TableView& t, size_t bwords, const u64* slot_of,
+                          const u32* alive, const u32* np, u32 np_cnt, u32* u0, u32 u0_cnt, u32* spare, const std::vector<u64>& inits,
+                          u32 k, u32 walk_steps) {
+        if constexpr (fair_slots_model<M> && M::MW <= LIVE_MW_MAX) {
+            constexpr int MW = M::MW;
+            const auto t0 = Clock::now();
+            const int dev = o_.device;
+            sg.ran = 1;
+            DBuf<u32> wbits, idx, rank, lrank, colour, stamp, comp, size, third, lvl;
+            DBuf<u64> or_me, or_took, wcb, lcb, out;
+            wbits.alloc(dev, bwords);
+            idx.alloc(dev, (size_t)cap_);
+            rank.alloc(dev, n);
+            comp.alloc(dev, n);
+            third.alloc(dev, np_cnt);
+            wcb.alloc(dev, (sizeof(LiveWeakCounters) + 7) / 8);
+            lcb.alloc(dev, (sizeof(LiveCounters) + 7) / 8);
+            LiveWeakCounters* wc = reinterpret_cast<LiveWeakCounters*>(wcb.p);
+            LiveCounters* lc = reinterpret_cast<LiveCounters*>(lcb.p);
+            LiveWeakCounters hw{};
+            constexpr size_t HEAD = offsetof(LiveWeakCounters, notme);  // (the masks behind it live across launches)
+            auto fail = [&](u32 err) {
+                if (err & LIVE_ERR_LOOKUP)
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: find_slot did not find a reachable state, or a successor of one, in the "
+                                                       "visited set (an engine error: such a state is never taken as \"not alive\")");
+                if (err & LIVE_ERR_STUCK)
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state of the witness has no successor of a lower rank, or a "
+                                                       "member of a level has no component");
+            };
+            auto clear_head = [&] { SR_HIP(hipMemsetAsync(wc, 0, HEAD, stream_)); };
+            auto read_w = [&] {  // the launch's counters (waits for it)
+                SR_HIP(hipGetLastError());
+                SR_HIP(hipMemcpyAsync(&hw, wc, sizeof(hw), hipMemcpyDeviceToHost, stream_));
+                SR_HIP(stream_sync(stream_));
+                fail(hw.err);
+            };
+            SR_HIP(hipMemsetAsync(wbits.p, 0, bwords * sizeof(u32), stream_));
+            SR_HIP(hipMemsetAsync(idx.p, 0xff, (size_t)cap_ * sizeof(u32), stream_));
+            SR_HIP(hipMemsetAsync(rank.p, 0xff, (size_t)n * sizeof(u32), stream_));
+            SR_HIP(hipMemsetAsync(comp.p, 0xff, (size_t)n * sizeof(u32), stream_));
+            SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), stream_));
+            if (u0_cnt) live_set_bits<><<<blocks_for(u0_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(u0, u0_cnt, slot_of, wbits.p);
+            if (np_cnt) live_index<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, wbits.p, idx.p, rank.p);
+            u32 *L = u0, *X = spare, *Y = third.p;
+            u32 cnt = u0_cnt;
+            // W: trimmed to the states with a successor in W (the progress trim's kernel on the W bitmap)
+            auto trim_w = [&] {
+                while (cnt) {
+                    LiveCounters h{};
+                    SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
+                    live_trim<M, true><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of, wbits.p, L, cnt, X, lc);
+                    SR_HIP(hipGetLastError());
+                    SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, stream_));
+                    SR_HIP(stream_sync(stream_));
+                    fail(h.err & LIVE_ERR_LOOKUP);
+                    if (h.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a trim round lists more states than W has");
+                    std::swap(L, X);
+                    cnt = h.next_n;
+                    sg.scc_rounds += 1;
+                    if (!h.removed) break;
+                }
+            };
+            trim_w();
+            sg.cyclic_states = cnt;
+            if (cnt) {  // what only the component search and the components' fairness need
+                colour.alloc(dev, n);
+                stamp.alloc(dev, n);
+                size.alloc(dev, n);
+                or_me.alloc(dev, (size_t)n * MW);
+                or_took.alloc(dev, (size_t)n * MW);
+                lvl.alloc(dev, cnt);
+                SR_HIP(hipMemsetAsync(stamp.p, 0, (size_t)n * sizeof(u32), stream_));
+            }
+            u32 round = 0;
+            u64 frozen = 0;
+            while (cnt) {  // one level of the tree
+                const u32 members = cnt;
+                SR_HIP(hipMemcpyAsync(lvl.p, L, (size_t)members * sizeof(u32), hipMemcpyDeviceToDevice, stream_));
+                live_level_open<MW><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(lvl.p, members, size.p, or_me.p, or_took.p);
+                // the components of W: colour, find the roots' components, take them out, until W is empty
+                while (cnt) {
+                    live_colour_init<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p);
+                    u32 *src = L, *dst = X, sn = cnt;
+                    while (sn) {
+                        clear_head();
+                        live_colour_push<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, wbits.p, colour.p, stamp.p,
+                                                                                                   ++round, src, sn, dst, wc);
+                        read_w();
+                        sg.scc_rounds += 1;
+                        if (hw.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a colouring round lists more states than W has");
+                        sn = hw.next_n;
+                        src = dst;
+                        dst = src == X ? Y : X;
+                    }
+                    live_scc_seed<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p, comp.p);
+                    src = L, dst = X, sn = cnt;
+                    for (;;) {
+                        clear_head();
+                        live_scc_join<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, wbits.p, colour.p, comp.p, src,
+                                                                                                sn, dst, wc);
+                        read_w();
+                        sg.scc_rounds += 1;
+                        if (hw.next_n > sn) throw Error(SR_ERR_HIP, "liveness: a join round lists more states than it was given");
+                        sn = hw.next_n;
+                        src = dst;
+                        dst = src == X ? Y : X;
+                        if (!hw.joined || !sn) break;
+                    }
+                    if (sn >= cnt) throw Error(SR_ERR_HIP, "liveness: a round of the component search took no state out of W");
+                    live_scc_leave<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, slot_of, comp.p, wbits.p);
+                    std::swap(L, src == X ? X : Y);  // (what has not joined is the next W of this search)
+                    cnt = sn;
+                }
+                // the level's components: accumulate, then freeze, drop or hand back every member
+                clear_head();
+                live_comp_acc_or<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, lvl.p, members, size.p,
+                                                                                                or_me.p, or_took.p, wc);
+                live_refine<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, slot_of, lvl.p, members, comp.p, size.p,
+                                                                                           or_me.p, or_took.p, wbits.p, L, wc);
+                read_w();
+                if (hw.next_n >= members) throw Error(SR_ERR_HIP, "liveness: a level of the decomposition removed no state from W");
+                if (hw.comps) sg.levels += 1;
+                sg.components += hw.comps;
+                sg.fair_components += hw.fair_comps;
+                frozen += hw.joined;
+                cnt = hw.next_n;
+                if (o_.verbose)
+                    std::fprintf(stderr, "[sr] liveness \"%s\" level %u: %u members, %u components (%u fair), %u back in W\n", m_.prop_name(p),
+                                 sg.levels, members, hw.comps, hw.fair_comps, cnt);
+                trim_w();
+            }
+            // the goal set, ranks towards it over F_p'
+            clear_head();
+            u32 sn = 0;
+            if (np_cnt) {
+                live_goal_strong<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, comp.p, rank.p, L, wc);
+                read_w();
+                sg.goal_states = sg.fair_states = hw.goal;
+                sn = hw.next_n;
+                if (hw.goal < frozen) throw Error(SR_ERR_HIP, "liveness: the goal set lost a frozen state");
+            }
+            auto reach = [&](u32* rk, u32* src, u32* dst, u32 todo) {  // levels until one ranks nothing
+                for (u32 level = 1; todo; ++level) {
+                    clear_head();
+                    live_reach<M><<<blocks_for(todo, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, rk, level, src, todo, dst, wc);
+                    read_w();
+                    sg.reach_rounds += 1;
+                    if (rk == rank.p) sg.fair_states += hw.joined;
+                    if (!hw.joined) break;
+                    todo = hw.next_n;
+                    std::swap(src, dst);
+                }
+            };
+            if (sg.goal_states) reach(rank.p, L, X, sn);
+            clear_head();
+            SR_HIP(hipMemsetAsync(&wc->first_init, 0xff, sizeof(u32), stream_));
+            live_first_ranked<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of, idx.p, rank.p, k, wc);
+            read_w();
+            if (hw.first_init < k) r.init_index = (int32_t)hw.first_init;
+            if (r.init_index >= 0) {
+                out.alloc(dev, ((size_t)walk_steps + 2) * W);
+                std::vector<u64> path(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
+                SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
+                const u64 bound = ((u64)A_ + 2) * (r.surviving + 1);  // the stem and A + 1 segments, each a simple path
+                auto descend = [&](const u32* rk, int then, u32 all) {  // (each launch but the last takes walk_steps steps)
+                    for (;;) {
+                        clear_head();
+                        live_descend<M><<<1, 64, 0, stream_>>>(m_, t, idx.p, rk, out.p, walk_steps, then, all, wc);
+                        read_w();
+                        if (hw.steps > walk_steps + 1) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
+                        const size_t o = path.size();
+                        path.resize(o + (size_t)hw.steps * W);
+                        if (hw.steps) {
+                            SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)hw.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
+                            SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)hw.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+                        }
+                        if (path.size() / W - 1 > bound) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than its bound");
+                        if (hw.end == LIVE_DESCEND_DONE) break;
+                        if (!hw.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
+                    }
+                };
+                descend(rank.p, -1, 0);
+                sg.stem_len = (int64_t)(path.size() / W - 1);
+                const u32 g = hw.last_idx;
+                if (g >= n) throw Error(SR_ERR_HIP, "liveness: the stem's last state has no arena index");
+                u32 root = ~0u;
+                SR_HIP(hipMemcpy(&root, comp.p + g, sizeof(u32), hipMemcpyDeviceToHost));
+                if (root == ~0u) {  // a sink of F_p': terminal, or a stutter end (live_accept checks which)
+                    u64 all = 0;
+                    for_each_successor(m_, &path[path.size() - W], [&](int, const u64*) { ++all; });
+                    sg.loop_len = 0;
+                    live_accept(p, r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true);
+                } else {
+                    if (root >= n) throw Error(SR_ERR_HIP, "liveness: the stem ends in a fair node without a root");
+                    u64 c_or[MW];
+                    SR_HIP(hipMemcpy(c_or, or_me.p + (size_t)root * MW, sizeof(c_or), hipMemcpyDeviceToHost));
+                    lrank.alloc(dev, n);
+                    SR_HIP(hipMemsetAsync(lrank.p, 0xff, (size_t)n * sizeof(u32), stream_));
+                    SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), stream_));  // (the stem's masks are not the loop's)
+                    live_members<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, comp.p, root, Y, wc);
+                    read_w();
+                    const u32 mcnt = hw.next_n;
+                    auto segment = [&](int plan, int a) {
+                        clear_head();
+                        live_targets<M><<<blocks_for(mcnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, root, plan, a, g, Y, mcnt,
+                                                                                                 lrank.p, L, wc);
+                        read_w();
+                        if (!hw.joined) throw Error(SR_ERR_NONDETERMINISM, "liveness: a segment of the closed walk has no target in its fair node");
+                        reach(lrank.p, L, X, hw.next_n);
+                        sg.segments += 1;
+                        descend(lrank.p, plan == LIVE_PLAN_TAKE ? a : -1, 1);
+                    };
+                    for (int a = 0; a < (int)A_; ++a)
+                        if (live_strong_plan(a, hw.taken, c_or) == LIVE_PLAN_TAKE) segment(LIVE_PLAN_TAKE, a);
+                    segment(LIVE_PLAN_HOME, 0);
+                    sg.loop_len = (int64_t)(path.size() / W - 1) - sg.stem_len;
+                    live_accept_weak(p, r, path, (size_t)sg.stem_len, true);
+                }
+            }
+            sg.pass_ms = secs(t0, Clock::now()) * 1e3;
+        } else {
+            (void)p, (void)r, (void)sg, (void)n, (void)t, (void)bwords, (void)slot_of, (void)alive, (void)np, (void)np_cnt, (void)u0, (void)u0_cnt,
+                (void)spare, (void)inits, (void)k, (void)walk_steps;
+            throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
+        }
+    }
+
     // The weak mode's lasso, replayed on the host model before it becomes the discovery of p: every step is a
     // successor in `actions()` order, the condition holds nowhere, no step returns its own state, the last
     // state equals the state at loop_start word for word, and the loop is weakly fair on its own states and
     // steps (live.hpp live_loop_fair). A path that fails is an engine error, never a discovery.
-    void live_accept_weak(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start) {
+    // strong (the strong mode's lasso): the loop is strongly fair instead (live_loop_strong_fair).
+    void live_accept_weak(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start, bool strong = false) {
         if constexpr (fair_slots_model<M>) {
             const size_t len = path.size() / W - 1;
             const std::string name = m_.prop_name(p);
@@ -1805,8 +2063,10 @@ class Engine final : public EngineBase {
                                                            "\" returns its own state (weak fairness steps over no self-loop)");
             if (loop_start >= len || !std::equal(&path[len * W], &path[len * W] + W, &path[loop_start * W]))
                 throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" does not end where it starts");
-            if (!live_loop_fair(m_, &path[loop_start * W], len - loop_start))
-                throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" is not weakly fair");
+            if (strong ? !live_loop_strong_fair(m_, &path[loop_start * W], len - loop_start)
+                       : !live_loop_fair(m_, &path[loop_start * W], len - loop_start))
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" is not " +
+                                                       (strong ? "strongly" : "weakly") + " fair");
             r.loop_start = (int64_t)loop_start;
             r.end_kind = SR_LIVE_END_LOOP;
             r.witness_len = (int64_t)len;

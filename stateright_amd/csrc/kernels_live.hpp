@@ -643,4 +643,162 @@ __global__ void __launch_bounds__(64) live_descend(M m, TableView t, const u32* 
     }
 }
 
+// ---- strong fairness (live.hpp: STRONG FAIRNESS). Launched only with sr_opts.liveness = SR_LIVENESS_STRONG,
+// after live_mark and the progress trim, in place of the weak mode's pass and over the same arrays. The
+// decomposition tree is built LEVEL BY LEVEL, all open components at once: W (a bitmap and a list) starts as
+// the weak mode's U; one level takes the components of G'[W] with the kernels above (colour, seed, join,
+// leave), accumulates per component, and refines:
+//   live_level_open     per member of the level: the accumulators at its index cleared. A root is the highest
+//                       arena index of its component and a member of its level, and the same index can be a
+//                       root again at a deeper level, so the accumulators are reset per level.
+//   live_comp_acc_or    live_comp_acc with the OR of the me masks in place of their AND (the in-wave reduction
+//                       as it is there). comp holds a number only for the members of THIS level and for frozen
+//                       states (live_refine clears every other), and a frozen component's root never returns
+//                       to W, so `comp[t] == root` is membership in the component of this level.
+//   live_refine         per member of the level, with bad = or_me & ~or_took of its component: in a component
+//                       of one state it leaves for good; in a fair node (bad empty) it is FROZEN, keeping its
+//                       component number for the goal set and the witness, and never returns to W; with
+//                       me(s) & bad != 0 it leaves for good; every other member returns to W (its bit set, a
+//                       place in next) with its number cleared. Roots count the nodes and the fair nodes.
+//   live_goal_strong    sinks (rank 0 from live_index) and frozen states get rank 0; the other states of F_p'
+//                       are listed for live_reach.
+// The witness runs on live_reach, live_first_ranked, live_members, live_targets (LIVE_PLAN_TAKE and
+// LIVE_PLAN_HOME only) and live_descend as they are.
+
+template <int MW>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_level_open(const u32* __restrict__ list, u32 n, u32* __restrict__ size,
+                                                              u64* __restrict__ or_me, u64* __restrict__ or_took) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    const u32 i = list[g];
+    size[i] = 0;
+#pragma unroll
+    for (int w = 0; w < MW; ++w) or_me[(size_t)i * MW + w] = or_took[(size_t)i * MW + w] = 0;
+}
+
+// or_me, or_took and size (zero before the launch: live_level_open) are by root.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_comp_acc_or(M m, const u64* __restrict__ arena, TableView t,
+                                                               const u32* __restrict__ idx, const u32* __restrict__ comp,
+                                                               const u32* __restrict__ list, u32 n, u32* size, u64* or_me,
+                                                               u64* or_took, LiveWeakCounters* lc) {
+    constexpr int MW = M::MW;
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    u32 root = ~0u;
+    u64 me[MW], took[MW];
+#pragma unroll
+    for (int w = 0; w < MW; ++w) me[w] = took[w] = 0;
+    if (g < n) {
+        const u32 i = list[g];
+        root = comp[i];
+        if (root != ~0u) {
+            u64 s[M::W];
+            load_state<M::W>(arena, i, s);
+            bool lost = false;
+            live_moving(m, s, me, [&](int a, const u64* ns) {
+                const u32 ti = live_idx_of(m, t, idx, ns, lost);
+                if (ti != ~0u && comp[ti] == root) took[a >> 6] |= 1ull << (a & 63);
+            });
+            if (lost) atomicOr(&lc->err, (u32)LIVE_ERR_LOOKUP);
+        }
+    }
+    const u64 active = __ballot(root != ~0u);
+    if (!active) return;
+    const int leader = __builtin_ctzll(active);
+    const u32 first = lane_u32(root, (u32)leader);
+    if (!__ballot(root != ~0u && root != first)) {  // the wave's members share one component
+#pragma unroll
+        for (int w = 0; w < MW; ++w) {
+            u64 e = me[w], o = took[w];  // (a lane without a member holds the neutral values)
+#pragma unroll
+            for (int d = 32; d; d >>= 1) {
+                e |= (u64)__shfl_xor((unsigned long long)e, d, 64);
+                o |= (u64)__shfl_xor((unsigned long long)o, d, 64);
+            }
+            if ((int)(threadIdx.x & 63) == leader) {
+                if (e) atomicOr((unsigned long long*)&or_me[(size_t)first * MW + w], (unsigned long long)e);
+                if (o) atomicOr((unsigned long long*)&or_took[(size_t)first * MW + w], (unsigned long long)o);
+            }
+        }
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&size[first], (u32)__popcll(active));
+    } else if (root != ~0u) {
+#pragma unroll
+        for (int w = 0; w < MW; ++w) {
+            if (me[w]) atomicOr((unsigned long long*)&or_me[(size_t)root * MW + w], (unsigned long long)me[w]);
+            if (took[w]) atomicOr((unsigned long long*)&or_took[(size_t)root * MW + w], (unsigned long long)took[w]);
+        }
+        atomicAdd(&size[root], 1u);
+    }
+}
+
+// list: the members of the level (every one has a component number). next takes the members that return to W
+// (a subset of list); lc->joined counts the members frozen in fair nodes, lc->comps and lc->fair_comps the
+// level's nodes and fair nodes.
+template <class M>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_refine(M m, const u64* __restrict__ arena, const u64* __restrict__ slot_of,
+                                                          const u32* __restrict__ list, u32 n, u32* __restrict__ comp,
+                                                          const u32* __restrict__ size, const u64* __restrict__ or_me,
+                                                          const u64* __restrict__ or_took, u32* w_bits, u32* __restrict__ next,
+                                                          LiveWeakCounters* lc) {
+    constexpr int MW = M::MW;
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool back = false, frozen = false, is_comp = false, is_fair = false, orphan = false;
+    u32 i = 0;
+    if (g < n) {
+        i = list[g];
+        const u32 root = comp[i];
+        orphan = root == ~0u;
+        if (!orphan && size[root] >= 2) {
+            const u64 *om = &or_me[(size_t)root * MW], *ot = &or_took[(size_t)root * MW];
+            frozen = live_strong_masks<MW>(om, ot);
+            is_comp = root == i;
+            is_fair = is_comp && frozen;
+            if (!frozen) {
+                u64 s[M::W], me[MW];
+                load_state<M::W>(arena, i, s);
+                live_moving(m, s, me, [](int, const u64*) {});
+                bool hit = false;
+#pragma unroll
+                for (int w = 0; w < MW; ++w) hit = hit || (me[w] & om[w] & ~ot[w]) != 0;
+                back = !hit;
+            }
+        }
+        if (!frozen) comp[i] = ~0u;
+        if (back) {
+            const u64 sl = slot_of[i];
+            atomicOr(&w_bits[sl >> 5], 1u << (sl & 31));
+        }
+    }
+    live_append(back, i, next, &lc->next_n);
+    const u64 zm = __ballot(frozen), cm = __ballot(is_comp), fm = __ballot(is_fair);
+    if ((threadIdx.x & 63) == 0) {
+        if (zm) atomicAdd(&lc->joined, (u32)__popcll(zm));
+        if (cm) atomicAdd(&lc->comps, (u32)__popcll(cm));
+        if (fm) atomicAdd(&lc->fair_comps, (u32)__popcll(fm));
+    }
+    if (__ballot(orphan) && (threadIdx.x & 63) == 0) atomicOr(&lc->err, (u32)LIVE_ERR_STUCK);
+}
+
+// list: the NP list. rank holds 0 for the sinks (live_index) and ~0 elsewhere; comp a number for the frozen
+// states only. next takes the states of F_p' without a rank; lc->goal counts the goal set.
+template <int = 0>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_goal_strong(const u32* __restrict__ list, u32 n, const u64* __restrict__ slot_of,
+                                                               const u32* alive, const u32* __restrict__ comp, u32* rank,
+                                                               u32* __restrict__ next, LiveWeakCounters* lc) {
+    const u32 g = blockIdx.x * LIVE_BLOCK + threadIdx.x;
+    bool todo = false, goal = false;
+    u32 i = 0;
+    if (g < n) {
+        i = list[g];
+        if (live_bit(alive, slot_of[i])) {
+            goal = rank[i] == 0;
+            if (!goal && comp[i] != ~0u) rank[i] = 0, goal = true;
+            todo = !goal;
+        }
+    }
+    live_append(todo, i, next, &lc->next_n);
+    const u64 gm = __ballot(goal);
+    if (gm && (threadIdx.x & 63) == 0) atomicAdd(&lc->goal, (u32)__popcll(gm));
+}
+
 }  // namespace sr

@@ -1102,6 +1102,85 @@ struct SpinLock {
     }
 };
 
+// -----------------------------------------------------------------------------------------------
+// FairRings(d, w, core, lanes): nested rings, the fixture of the complete `eventually` check's
+// strong-fairness mode (live.hpp; no reference counterpart). Lane j < lanes has the rings 0 .. d_j,
+// d_j = 1 + (j mod d), of w positions each, and one `done` state. One word, and the packed key is
+// the word, declared 8 bits wider as SpinLock's is:
+//   [0,6)    x     the position on the ring, x < w (4 <= w <= 64)
+//   [6,11)   k     the ring, k <= d_j (1 <= d <= 28)
+//   [11,20)  j     the lane (1 <= lanes <= 512)
+//   20       done
+// Slots, 2d + 3 of them, each a fairness class (FAIR_SLOTS); no step is a no-op:
+//   0          Step    (k, x) -> (k, (x + 1) mod w), always enabled off `done`
+//   1 + k      Out(k)  enabled at (k, 0): for k = 0 to the lane's `done` state, else to (k - 1, 0); where
+//                      the lane's CORE is on (core == 1, or core == 2 and j is odd) and k = d_j, also
+//                      enabled at (k, 2), leading to (k, 0)
+//   d + 2 + k  In(k)   enabled at (k, 1) iff k < d_j: to (k + 1, 1)
+// `done` is terminal. One property, eventually "done"; init states (j, 0, 0) for every lane.
+// A lane is one strongly connected component and unfair under strong fairness (Out(0) leaves it);
+// without the states that enable Out(0) the rings 1 .. d_j are one and Out(1) leaves them, and so on
+// inwards: the innermost ring is a component at depth d_j + 1, fair iff the core is on. So the
+// property holds under strong fairness iff core = 0, and weak fairness refutes it in every lane.
+// lanes + sum_j (d_j + 1) w states.
+// -----------------------------------------------------------------------------------------------
+struct FairRings {
+    static constexpr int W = 1, MW = 1, NPROPS = 1;
+    static constexpr bool FAIR_SLOTS = true;
+    static constexpr bool SELF_LOOPS_EXACT = true;  // every enabled slot changes the state
+    static constexpr u64 DONE = 1ull << 20;
+    int d, w, core, lanes;
+    int max_actions() const { return 2 * d + 3; }
+    int max_out_degree() const { return 2; }
+    u32 emask() const { return 1u; }
+    SR_HD static u64 pack(u32 j, u32 k, u32 x) { return (u64)x | (u64)k << 6 | (u64)j << 11; }
+    SR_HD u32 depth_of(u32 j) const { return 1u + j % (u32)d; }
+    SR_HD bool core_on(u32 j) const { return core == 1 || (core == 2 && (j & 1)); }
+    SR_HD void enabled(const u64* sp, u64* m) const {
+        const u64 s = sp[0];
+        const u32 x = (u32)(s & 63), k = (u32)(s >> 6 & 31), j = (u32)(s >> 11 & 511);
+        u64 e = 0;
+        if (!(s & DONE)) {
+            e = 1;
+            if (x == 0 || (x == 2 && k == depth_of(j) && core_on(j))) e |= 1ull << (1 + k);
+            if (x == 1 && k < depth_of(j)) e |= 1ull << (d + 2 + k);
+        }
+        m[0] = e;
+    }
+    SR_HD bool apply(const u64* sp, int a, u64* o) const {
+        const u64 s = sp[0];
+        const u32 x = (u32)(s & 63), k = (u32)(s >> 6 & 31), j = (u32)(s >> 11 & 511);
+        if (a == 0) o[0] = pack(j, k, x + 1 == (u32)w ? 0 : x + 1);
+        else if (a <= d + 1) o[0] = x ? pack(j, k, 0) : k ? pack(j, k - 1, 0) : pack(j, 0, 0) | DONE;
+        else o[0] = pack(j, k + 1, 1);
+        return true;
+    }
+    SR_HD bool discovers(int, const u64* sp) const { return (sp[0] & DONE) != 0; }  // the condition holds
+    int init_count() const { return lanes; }
+    int init_states(u64* out) const {
+        for (int j = 0; j < lanes; ++j) out[j] = pack((u32)j, 0, 0);
+        return lanes;
+    }
+    int expectation(int) const { return EVENTUALLY; }
+    const char* prop_name(int) const { return "done"; }
+    int qkey_bits() const { return 29; }
+    SR_HD unsigned __int128 qkey(const u64* s) const { return s[0]; }
+    int describe_width() const { return 4; }
+    void describe(const u64* s, i64* o) const {
+        o[0] = (i64)(s[0] >> 11 & 511);
+        o[1] = (i64)(s[0] >> 6 & 31);
+        o[2] = (i64)(s[0] & 63);
+        o[3] = (i64)(s[0] >> 20 & 1);
+    }
+    void undescribe(const i64* o, u64* s) const { s[0] = pack((u32)o[0] & 511, (u32)o[1] & 31, (u32)o[2] & 63) | (o[3] & 1 ? DONE : 0); }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return 2 * d + 3; }
+    std::string action_name(i64 id) const {
+        if (id == 0) return "Step";
+        return std::string(id <= d + 1 ? "Out(" : "In(") + std::to_string(id <= d + 1 ? id - 1 : id - d - 2) + ")";
+    }
+};
+
 // Models whose action slots are fairness classes (`static constexpr bool FAIR_SLOTS = true`): the
 // complete `eventually` check's weak-fairness mode (live.hpp) treats every slot as one action that
 // a fair run may not ignore for ever. Where a slot is a network position or a queue entry (the actor

@@ -56,6 +56,7 @@ std::unique_ptr<EngineBase> reg_registers_wide(const EngineArgs& a);  // ABD, 16
 std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spread fixture (W = 1, 2, 4), LiveGraph
 std::unique_ptr<EngineBase> reg_two_phase_live(const EngineArgs& a);  // 2pc with `eventually` properties (TwoPhaseLive)
 std::unique_ptr<EngineBase> reg_spin_lock(const EngineArgs& a);       // SpinLock
+std::unique_ptr<EngineBase> reg_fair_rings(const EngineArgs& a);      // FairRings
 
 // SpinLock (models.hpp) of (threads), handed to f: the engine (reg_spin_lock.hip) and the host-only entry
 // points (engine.hip) validate alike.
@@ -64,6 +65,18 @@ auto with_spin_lock(const i64* p, int np, F&& f) {
     if (np < 1) throw Error(SR_ERR_ARG, "spin-lock needs 1 param (threads)");
     if (p[0] < 1 || p[0] > 20) throw Error(SR_ERR_UNSUPPORTED, "spin-lock: threads must be in 1..=20");
     return f(SpinLock{(int)p[0]});
+}
+
+// FairRings (models.hpp) of (d, w, core, lanes), handed to f: the engine (reg_fair_rings.hip) and the
+// host-only entry points (engine.hip) validate alike.
+template <class F>
+auto with_fair_rings(const i64* p, int np, F&& f) {
+    if (np < 4) throw Error(SR_ERR_ARG, "fair-rings needs 4 params (d, w, core, lanes)");
+    if (p[0] < 1 || p[0] > 28) throw Error(SR_ERR_UNSUPPORTED, "fair-rings: d must be in 1..=28");
+    if (p[1] < 4 || p[1] > 64) throw Error(SR_ERR_UNSUPPORTED, "fair-rings: w must be in 4..=64");
+    if (p[2] < 0 || p[2] > 2) throw Error(SR_ERR_ARG, "fair-rings: core must be 0, 1 or 2");
+    if (p[3] < 1 || p[3] > 512) throw Error(SR_ERR_UNSUPPORTED, "fair-rings: lanes must be in 1..=512");
+    return f(FairRings{(int)p[0], (int)p[1], (int)p[2], (int)p[3]});
 }
 
 // TwoPhaseLive (models.hpp) of (rm_count), handed to f: the engines (reg_two_phase_live.hip) and the

@@ -75,6 +75,26 @@ class SpinLockSys(_Model):
         return [self.threads]
 
 
+class FairRings(_Model):
+    """Nested rings (csrc/models.hpp `FairRings`; no reference counterpart): the fixture of
+    `strong_fairness()`. Lane j < lanes has the rings 0 .. d_j, d_j = 1 + (j mod d), of w positions each;
+    Step walks round a ring, Out(k) leaves ring k at position 0 (ring 0 for the lane's terminal `done`
+    state), In(k) enters ring k + 1 at position 1. A lane whose core is on (core == 1, or core == 2 and j
+    odd) can also take Out(d_j) at position 2 of its innermost ring and stay there. One `eventually`
+    property "done": `weak_fairness()` refutes it in every lane; under `strong_fairness()` it holds iff
+    core == 0, and the fair set of a core lane lies d_j levels deep inside components that are not fair.
+    1 <= d <= 28, 4 <= w <= 64, core in (0, 1, 2), 1 <= lanes <= 512."""
+    MODEL_ID = N.SR_MODEL_FAIR_RINGS
+
+    def __init__(self, d, w, core, lanes):
+        if not (1 <= d <= 28 and 4 <= w <= 64 and core in (0, 1, 2) and 1 <= lanes <= 512):
+            raise ValueError("FairRings: d in 1..=28, w in 4..=64, core in (0, 1, 2), lanes in 1..=512")
+        self.d, self.w, self.core, self.lanes = d, w, core, lanes
+
+    def params(self):
+        return [self.d, self.w, self.core, self.lanes]
+
+
 class Increment(_Model):
     """`increment` example `State::new(n)` (examples/increment.rs:109-197)."""
     MODEL_ID = N.SR_MODEL_INCREMENT
