@@ -43,6 +43,13 @@ constexpr int MAX_PARTS = 64;  // visited-set partitions (one per GPU, or virtua
 #ifndef SR_STAGE_WORDS
 #define SR_STAGE_WORDS 1024
 #endif
+// expand_fast's stage of narrow states as one region per wave (1) or one span shared by the
+// workgroup's waves (0): a wave's new states, the children of neighbouring parents, stay adjacent
+// in the next frontier and meet in one workgroup's duplicate filter there (DESIGN.md §3 "stage
+// regions"). One-word states only: wider ones keep the shared stage (see expand_fast).
+#ifndef SR_STAGE_PER_WAVE
+#define SR_STAGE_PER_WAVE 1
+#endif
 // expand_fast's dynamic chunks: on a level of many chunks per workgroup (> DYN_MIN_RATIO), each
 // workgroup takes three chunks statically and then pulls the next ones from a counter, so that the
 // workgroups finish the level together (0: static striding only).
@@ -1097,8 +1104,31 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     static_assert(MW * 64 <= 1024, "action ids must fit 10 bits");
     __shared__ u16 smap[WPB][MAPCAP];
     __shared__ u32 stage_n, base, scratch[2 * WPB];
+    // Stage regions (SR_STAGE_PER_WAVE, one-word states): wave w appends only to entries [w REG,
+    // (w + 1) REG) of the stage, its fill wfill a wave-uniform register (no LDS atomic, no leader,
+    // no read-back per append); what does not fit its region goes straight to the next frontier.
+    // At each chunk end the wave leaves in fill[w] its fill (bits 0-15) and whether its region might
+    // not hold another chunk like the one just finished (bit 16, the flush rule below). At the flush
+    // each wave copies its own region behind the earlier waves', so a wave's states stay adjacent
+    // and in its append order.
+    // Two groups of instantiations keep the shared stage, because the regions cost them registers
+    // (compiler remarks, profiles/r09_stage_regions.txt): the queue form of every model but plain 2pc
+    // (`enabled_moves`, exact, no `eventually` bits: its queue forms stay at 80 VGPRs and 6 waves per
+    // SIMD; the others ran 7 waves at 71-72 VGPRs and took 73-75, canonical and liveness 2pc spilled
+    // more VGPRs) and the counting rounds form of canonical 2pc (79 -> 81 VGPRs, 6 -> 5 waves).
+    // One-word states only: increment_lock N=10 (two words, every successor new, no filter for the
+    // order to help) was 0.5 % slower with regions, beyond the parent's spread.
+    constexpr bool REGIONS = SR_STAGE_PER_WAVE && W == 1 &&
+                             (PB > 0 || (has_enabled_moves<M>::value && exact_moves_model<M> && !has_emask<M>::value)) &&
+                             !(is_canon<M>::value && STATS && PB > 0);
+    constexpr u32 REG = (u32)STAGE / (u32)WPB;
+    static_assert(!REGIONS || (REG >= 64 && REG < 65536), "a region holds a round and fits fill's 16 bits");
+    __shared__ __attribute__((aligned(16))) u32 fill[WPB];
+    u32 wfill = 0;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const u32 rbase = REGIONS ? lane_u32((u32)wid * REG, 0) : 0u;  // the wave's region (a scalar)
     if (threadIdx.x == 0) stage_n = 0;
+    if (REGIONS && threadIdx.x < (u32)WPB) fill[threadIdx.x] = 0;
     // The previous level's publish and the slot reset (SlotWork) run in one extra workgroup, the
     // last of the grid: in a small level any workgroup that expands parents is on the critical
     // path, and the publish waits for its host stores to be acknowledged.
@@ -1343,10 +1373,17 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
             const u32 cnt = __popcll(mask);
             const u32 below = __popcll(mask & ((1ull << lane) - 1));
             const int leader = __builtin_ctzll(mask);
-            u32 sb = 0;
-            if (lane == leader) sb = atomicAdd(&stage_n, cnt);
-            sb = lane_u32(sb, (u32)leader);
-            const u32 in_stage = sb >= (u32)STAGE ? 0u : min(cnt, (u32)STAGE - sb);
+            u32 sb = 0, in_stage;
+            if constexpr (REGIONS) {
+                sb = wfill;  // (<= REG)
+                in_stage = min(cnt, REG - sb);
+                wfill = sb + in_stage;
+                sb += rbase;
+            } else {
+                if (lane == leader) sb = atomicAdd(&stage_n, cnt);
+                sb = lane_u32(sb, (u32)leader);
+                in_stage = sb >= (u32)STAGE ? 0u : min(cnt, (u32)STAGE - sb);
+            }
             u32 gb = 0;
             if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
             gb = lane_u32(gb, (u32)leader);
@@ -1628,10 +1665,17 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
                 const u32 cnt = __popcll(mask);
                 const u32 below = __popcll(mask & ((1ull << lane) - 1));
                 const int leader = __builtin_ctzll(mask);
-                u32 sb = 0;
-                if (lane == leader) sb = atomicAdd(&stage_n, cnt);
-                sb = lane_u32(sb, (u32)leader);
-                const u32 in_stage = sb >= (u32)STAGE ? 0u : min(cnt, (u32)STAGE - sb);
+                u32 sb = 0, in_stage;
+                if constexpr (REGIONS) {
+                    sb = wfill;  // (<= REG)
+                    in_stage = min(cnt, REG - sb);
+                    wfill = sb + in_stage;
+                    sb += rbase;
+                } else {
+                    if (lane == leader) sb = atomicAdd(&stage_n, cnt);
+                    sb = lane_u32(sb, (u32)leader);
+                    in_stage = sb >= (u32)STAGE ? 0u : min(cnt, (u32)STAGE - sb);
+                }
                 u32 gb = 0;
                 if (cnt > in_stage && lane == leader) gb = atomicAdd(&lc->claims, cnt - in_stage);
                 gb = lane_u32(gb, (u32)leader);
@@ -1680,29 +1724,66 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
             s_cnext = cn;
         }
         first_chunk = false;
+        if constexpr (REGIONS) {
+            // The flush rule, per wave: another chunk like this one (d states staged), and a quarter
+            // more, would not fit the region. A region that overflowed is full and asks for the flush.
+            if (lane == 0) {
+                const u32 d = wfill - (fill[wid] & 0xffffu);
+                fill[wid] = wfill | (wfill + d + d / 4 > REG ? 1u << 16 : 0u);
+            }
+        }
         __syncthreads();
         c0 = c_next;
         c_next = dyn ? s_cnext : c_next + cstride;  // (s_cnext is rewritten only after the next chunk-end barrier)
-        if (stage_n >= (u32)STAGE / 2) {
-            const u32 nst = min(stage_n, (u32)STAGE);
+        // The flush: one reservation for the whole stage. Shared stage: the threads copy entries
+        // 0 .. nst - 1. Regions: wave w copies its own region, in append order, to the positions
+        // behind the earlier regions' (before: the sum of their fills), so the span holds the
+        // regions in wave order.
+        u32 nst, before = 0;
+        bool flush;
+        if constexpr (REGIONS) {
+            u32 flags = 0;
+            nst = 0;
+#pragma unroll
+            for (int w = 0; w < WPB; ++w) {
+                const u32 f = fill[w];
+                if (w < wid) before += f & 0xffffu;
+                nst += f & 0xffffu;
+                flags |= f;
+            }
+            flush = nst && ((flags >> 16) != 0 || nst >= (u32)STAGE / 2);
+        } else {
+            nst = min(stage_n, (u32)STAGE);
+            flush = stage_n >= (u32)STAGE / 2;
+        }
+        if (flush) {
             if (threadIdx.x == 0) base = atomicAdd(&lc->claims, nst);
             __syncthreads();
-            for (u32 i = threadIdx.x; i < nst; i += blockDim.x) {
-                const u32 pos = base + i;
+            const u32 i0 = REGIONS ? (u32)lane : threadIdx.x, i1 = REGIONS ? wfill : nst;
+            for (u32 i = i0; i < i1; i += REGIONS ? 64u : blockDim.x) {
+                const u32 pos = base + before + i;
+                const u32 k = rbase + i;  // its stage entry
                 u64 ns[W];
 #pragma unroll
-                for (int x = 0; x < W; ++x) ns[x] = stage[i * W + x];
+                for (int x = 0; x < W; ++x) ns[x] = stage[k * W + x];
                 if (pos < next_cap) {
                     store_state<W>(next, pos, ns);
-                    next_par[pos] = stage_par[i];
-                    if (sw.naeb) sw.naeb[pos] = sw.peb[stage_par[i]];
+                    next_par[pos] = stage_par[k];
+                    if (sw.naeb) sw.naeb[pos] = sw.peb[stage_par[k]];
                 } else {
                     atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
                 }
                 eval_props(m, ns, pos, undiscovered, lc);
             }
-            __syncthreads();
-            if (threadIdx.x == 0) stage_n = 0;
+            if constexpr (REGIONS) {
+                // (no barrier: the wave has copied its own region, and the other waves read fill
+                // before the barrier above and again only behind the next chunk's barriers)
+                wfill = 0;
+                if (lane == 0) fill[wid] = 0;
+            } else {
+                __syncthreads();
+                if (threadIdx.x == 0) stage_n = 0;
+            }
         }
     }
     if (dyn && threadIdx.x == 0 && atomicAdd(&lc->chunk_done, 1u) == nblk - 1) {
@@ -1716,7 +1797,18 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     // The stage's span of the next frontier is reserved first; the round trip of that atomic
     // overlaps the block's reduction of its statistics (both sums in one pass).
     __syncthreads();  // the stage's fill is final
-    const u32 n = min(stage_n, (u32)STAGE);
+    u32 n, before = 0;  // (regions: as at the chunk-end flush; fill is as the last chunk end left it)
+    if constexpr (REGIONS) {
+        n = 0;
+#pragma unroll
+        for (int w = 0; w < WPB; ++w) {
+            const u32 f = fill[w] & 0xffffu;
+            if (w < wid) before += f;
+            n += f;
+        }
+    } else {
+        n = min(stage_n, (u32)STAGE);
+    }
     u32 my_base = 0;
     if (threadIdx.x == 0 && n) my_base = atomicAdd(&lc->claims, n);
     u32 total_succ, total_enabled;
@@ -1729,15 +1821,17 @@ __global__ void __launch_bounds__(64 * expand_wpb<M>()) __attribute__((amdgpu_wa
     }
     SR_TL(7);
     __syncthreads();
-    for (u32 i = threadIdx.x; i < n; i += blockDim.x) {
-        u32 pos = base + i;
+    const u32 i0 = REGIONS ? (u32)lane : threadIdx.x, i1 = REGIONS ? wfill : n;
+    for (u32 i = i0; i < i1; i += REGIONS ? 64u : blockDim.x) {
+        u32 pos = base + before + i;
+        const u32 k = rbase + i;
         u64 ns[W];
 #pragma unroll
-        for (int x = 0; x < W; ++x) ns[x] = stage[i * W + x];
+        for (int x = 0; x < W; ++x) ns[x] = stage[k * W + x];
         if (pos < next_cap) {
             store_state<W>(next, pos, ns);
-            next_par[pos] = stage_par[i];
-            if (sw.naeb) sw.naeb[pos] = sw.peb[stage_par[i]];
+            next_par[pos] = stage_par[k];
+            if (sw.naeb) sw.naeb[pos] = sw.peb[stage_par[k]];
         } else {
             atomicOr(&lc->err, (u32)ERR_FRONTIER_OVERFLOW);
         }
