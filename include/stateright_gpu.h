@@ -800,6 +800,45 @@ int32_t sr_model_fingerprint(int32_t model_id, const int64_t* params, int32_t np
  * it. Returns the states checked, or SR_ERR_* (sr_last_error says which state failed). */
 int64_t sr_selftest_describe(int32_t model_id, const int64_t* params, int32_t nparams, int64_t max_states);
 
+/* ---- the visited-set audit (csrc/kernels_audit.hpp) ----
+ * A check run with sr_opts.counters audits its final visited set against its arena, which lists
+ * every visited state, after the level loop: one pass over the slots and one over the arena's
+ * states (a partitioned check: every partition's table against that partition's states, summed over
+ * partitions and ranks). 72 bytes.
+ * Clean: misplaced, duplicates, arena_missing, arena_shared and meta_wrong are all 0, and
+ * occupied == arena_states == unique_state_count when the check explored everything. After an early
+ * exit (every property discovered inside a level) or a target stop, the level being expanded at the
+ * stop, or a speculative one enqueued past it, has claimed slots for states no arena level lists:
+ * then only occupied >= arena_states holds. Init states the model lists twice are two arena states
+ * of one slot and count in arena_shared. The audit proves that table and arena are equal as sets
+ * (and in FIFO order that meta names each state's level and parent); it says nothing about states
+ * that were never claimed. */
+typedef struct sr_table_audit {
+    uint32_t ran;            /* 1: the audit ran (sr_opts.counters); else every field is 0           */
+    uint32_t fifo;           /* 1: FIFO order, meta was audited                                      */
+    uint64_t slots;          /* slots of the final table(s)                                          */
+    uint64_t occupied;       /* non-zero slots                                                       */
+    uint64_t misplaced;      /* occupied slots whose stored displacement is at or past the probe limit,
+                                whose key cannot have that home, or with a vacant slot between their
+                                home and themselves                                                   */
+    uint64_t duplicates;     /* occupied slots whose key another slot in [home, slot) holds too       */
+    uint64_t arena_states;   /* states in the arena (every level the check accounted for)            */
+    uint64_t arena_missing;  /* ... that a lookup does not find in the table                          */
+    uint64_t arena_shared;   /* ... that resolve to a slot another arena state resolved to before     */
+    uint64_t meta_wrong;     /* FIFO order: ... whose slot's meta is not (own level, parent's rank);
+                                level 0 carries 0                                                    */
+} sr_table_audit;
+/* Copies at most `size` bytes of the finished check's audit; returns the engine's
+ * sizeof(sr_table_audit), or SR_ERR_ARG. */
+int32_t sr_gpu_bfs_table_audit(const sr_bfs* bfs, sr_table_audit* out, uint32_t size);
+/* GPU self-test of the visited set's growth kernels (rehash, rehash_ranges<u32|u64>, rehash_spill,
+ * remap_slots; csrc/rehash_selftest.hpp) on synthetic tables built on the host, grown through the
+ * engines' own launch routine and compared slot by slot with a sequential host rebuild. SR_OK, or
+ * SR_ERR_ARG with the first failing case in sr_last_error (SR_ERR_HIP: a runtime error).
+ * device < 0: host only, nothing is launched: every case is built and its expectations checked
+ * against the host model (the random fill must spill, the long run must extend its window twice). */
+int32_t sr_selftest_rehash_gpu(int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

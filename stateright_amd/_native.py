@@ -195,6 +195,24 @@ class sr_stats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class sr_table_audit(ctypes.Structure):
+    _fields_ = [
+        ("ran", ctypes.c_uint32),
+        ("fifo", ctypes.c_uint32),
+        ("slots", ctypes.c_uint64),
+        ("occupied", ctypes.c_uint64),
+        ("misplaced", ctypes.c_uint64),
+        ("duplicates", ctypes.c_uint64),
+        ("arena_states", ctypes.c_uint64),
+        ("arena_missing", ctypes.c_uint64),
+        ("arena_shared", ctypes.c_uint64),
+        ("meta_wrong", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class sr_dist_host_opts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
@@ -333,6 +351,8 @@ SIGNATURES = [
     ("sr_selftest_describe", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int64]),
     ("sr_gpu_bfs_spawn_partitioned", _P, [_P, ctypes.c_int32, ctypes.c_int32, _I64P, ctypes.c_int32,
                                           ctypes.POINTER(sr_opts)]),
+    ("sr_gpu_bfs_table_audit", ctypes.c_int32, [_P, ctypes.POINTER(sr_table_audit), ctypes.c_uint32]),
+    ("sr_selftest_rehash_gpu", ctypes.c_int32, [ctypes.c_int32]),
 ]
 
 SR_DIST_ID_BYTES = 128

@@ -589,6 +589,18 @@ class GpuBfsChecker:
         self._lib.sr_gpu_bfs_stats_sized(self._h, ctypes.byref(s), ctypes.sizeof(s))
         return s.as_dict()
 
+    def table_audit(self):
+        """The visited-set audit of a check run with `counters()` (csrc/kernels_audit.hpp), a dict of
+        sr_table_audit: ran, fifo, slots, occupied, misplaced, duplicates, arena_states, arena_missing,
+        arena_shared, meta_wrong. Clean: the last five but arena_states are 0 and, for a check that
+        explored everything, occupied == arena_states == unique_state_count() (after an early exit
+        only occupied >= arena_states). ran is 0 without `counters()`."""
+        a = N.sr_table_audit()
+        st = self._lib.sr_gpu_bfs_table_audit(self._h, ctypes.byref(a), ctypes.sizeof(a))
+        if st < 0:
+            raise CheckerError("sr_gpu_bfs_table_audit", st)
+        return a.as_dict()
+
     def liveness(self, name):
         """The complete `eventually` check's outcome for property `name` (`complete_liveness()`), a dict:
         ran (0: the option is off, `name` is no `eventually` property, the search itself discovered it,

@@ -1524,30 +1524,17 @@ class DistEngine final : public EngineBase {
         if (!o_.capacity_hint)
             while ((double)want > std::min(part_load_, lmax(old_cap * f)) * (double)(old_cap * f) && f < 64) f *= 2;
         p.cap = old_cap * f;
-        const TableView from = make_table_view(m_, ok.p, nullptr, old_cap), to0 = make_table_view(m_, nullptr, nullptr, p.cap);
-        u32 lg = 0;
-        while ((1ull << lg) < f) ++lg;
-        const u64 S = to0.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
-        // range by range as in Engine::launch_rehash (no clear of the new table), else clear + CAS
-        const bool ranges = rehash_by_ranges(from, to0, lg, p.cap);
-        p.keys.alloc(o_.device, p.words());
-        if (ranges) {
-            const u64 nranges = p.cap / S, spill_cap = nranges + 65536;
-            if (spill_.n < spill_cap + 1) spill_.alloc(o_.device, spill_cap + 1);
-            SR_HIP(hipMemsetAsync(spill_.p, 0, sizeof(u64), stream_));
-            if (to0.s32)
-                rehash_ranges<u32><<<(u32)nranges, REBUILD_BLOCK, 0, stream_>>>(from, old_cap, p.view(), lg, spill_.p,
-                                                                               spill_cap, &p.lc->err);
-            else
-                rehash_ranges<u64><<<(u32)nranges, REBUILD_BLOCK, 0, stream_>>>(from, old_cap, p.view(), lg, spill_.p,
-                                                                               spill_cap, &p.lc->err);
-            SR_HIP(hipGetLastError());
-            rehash_spill<<<256, 256, 0, stream_>>>(from, p.view(), spill_.p, spill_cap, &p.lc->err);
-        } else {
-            SR_HIP(hipMemsetAsync(p.keys.p, 0, p.words() * 8, stream_));
-            rehash<<<blocks_for(old_cap, 256), 256, 0, stream_>>>(from, old_cap, p.view(), &p.lc->err);
-        }
-        SR_HIP(hipGetLastError());
+        const TableView from = make_table_view(m_, ok.p, nullptr, old_cap);
+        // the engines' one growth routine (kernels.hpp): range by range without a clear of the new
+        // table, else clear + CAS
+        launch_rehash(
+            from, old_cap, make_table_view(m_, nullptr, nullptr, p.cap), p.cap, true,
+            [&](bool ranges) {
+                p.keys.alloc(o_.device, p.words());
+                if (!ranges) SR_HIP(hipMemsetAsync(p.keys.p, 0, p.words() * 8, stream_));
+                return p.view();
+            },
+            spill_, o_.device, &p.lc->err, stream_);
         SR_HIP(stream_sync(stream_));
         stats.rehashes++;
     }
@@ -1571,6 +1558,7 @@ class DistEngine final : public EngineBase {
         for (auto& d : disc) d = DiscoveryRec{};
         disc_at_.assign(M::NPROPS, DiscAt{});
         stats = sr_stats{};
+        audit = sr_table_audit{};
         stats.words_per_state = W;
         stats.order_used = SR_ORDER_FAST;
         stats.restarts = restarts_;
@@ -1841,7 +1829,59 @@ class DistEngine final : public EngineBase {
         stats.table_capacity = parts_[0].cap * T_;
         stats.displacement_limit = parts_[0].view().plimit;
         stats.table_encoding = table_encoding_word(parts_[0].view(), filt_log2_, false);
+        table_audit();
     }
+
+    // Owned by partition `part` of `nparts` (the replicated head's states, which every rank holds).
+    struct AuditKeepOwned {
+        u32 part, nparts;
+        __device__ bool operator()(const M& m, const u64* s) const { return part_of(m, s, state_fp<M>(s), nparts) == part; }
+    };
+    // The visited-set audit (kernels_audit.hpp, sr_opts.counters) of every partition's table against
+    // that partition's states: its own arena, and its share of the replicated head's levels before
+    // the hand-over, which take_owned put into its table and only the head arena lists. Summed over
+    // the partitions of this process and, with ranks, over the ranks (every rank runs with the same
+    // options, so all of them reach the collective). A check that ended inside the head has empty
+    // partitions: the head's own table is audited against the head arena (the same on every rank,
+    // not summed).
+    void table_audit() {
+        if (!o_.counters) return;
+        SR_HIP(stream_sync(stream_));
+        DBuf<u64> acc;
+        acc.alloc(o_.device, sizeof(AuditCounters) / 8 + 1);  // + the slots
+        SR_HIP(hipMemsetAsync(acc.p, 0, sizeof(AuditCounters) + 8, stream_));
+        AuditCounters* a = reinterpret_cast<AuditCounters*>(acc.p);
+        std::vector<DBuf<u32>> marks(parts_.size() + 1);
+        u64 slots = 0;
+        if (head_done_) {
+            const TableView hv = make_table_view(m_, hkeys_.p, nullptr, hcap_);
+            marks.back().alloc(o_.device, (size_t)((hcap_ + 31) / 32));
+            launch_audit_table(hv, hcap_, marks.back().p, a, stream_);
+            launch_audit_arena(m_, hv, harena_.p, nullptr, hlstart_.back(), nullptr, 0, 1, marks.back().p, a, stream_);
+            slots = hcap_;
+        } else {
+            const u64 head_n = stats.head_levels ? hlstart_[lvl0_] : 0;  // head states of the levels before the hand-over
+            for (size_t i = 0; i < parts_.size(); ++i) {
+                Part& p = parts_[i];
+                marks[i].alloc(o_.device, (size_t)((p.cap + 31) / 32));
+                launch_audit_table(p.view(), p.cap, marks[i].p, a, stream_);
+                launch_audit_arena(m_, p.view(), p.arena.p, nullptr, gl_off_[p.id], nullptr, 0, 1, marks[i].p, a, stream_);
+                launch_audit_arena(m_, p.view(), harena_.p, nullptr, head_n, nullptr, 0, 1, marks[i].p, a, stream_,
+                                   AuditKeepOwned{p.id, T_});
+                slots += p.cap;
+            }
+            SR_HIP(hipMemcpyAsync(acc.p + sizeof(AuditCounters) / 8, &slots, 8, hipMemcpyHostToDevice, stream_));
+            if (comm_) comm_->all_reduce(acc.p, sizeof(AuditCounters) / 8 + 1, RedOp::Sum, stream_);
+        }
+        u64 h[sizeof(AuditCounters) / 8 + 1];
+        SR_HIP(hipMemcpyAsync(h, acc.p, sizeof(h), hipMemcpyDeviceToHost, stream_));
+        SR_HIP(stream_sync(stream_));
+        AuditCounters c;
+        std::memcpy(&c, h, sizeof(c));
+        audit = sr_table_audit{1u, 0u, head_done_ ? slots : h[sizeof(AuditCounters) / 8], c.occupied, c.misplaced, c.duplicates,
+                               c.arena_states, c.arena_missing, c.arena_shared, c.meta_wrong};
+    }
+    u64 hcap_ = 0;  // slots of the replicated head's table (run_head)
 
     // ---- pipelined level loop ------------------------------------------------------------------
     // No host wait inside a level. Level L is enqueued as expand_route -> ONE all-to-all of
@@ -1873,6 +1913,7 @@ class DistEngine final : public EngineBase {
         }
         SR_HIP(hipMemsetAsync(hkeys_.p, 0, hwords * 8, stream_));
         const TableView hv = make_table_view(m_, hkeys_.p, nullptr, hcap);
+        hcap_ = hcap;
         hlstart_.assign(1, 0);
         SR_HIP(hipMemcpyAsync(harena_.p, rev.data(), rev.size() * 8, hipMemcpyHostToDevice, stream_));
         SR_HIP(hipMemsetAsync(hpar_.p, 0xff, (size_t)k * 4, stream_));

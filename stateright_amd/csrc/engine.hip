@@ -7,6 +7,7 @@
 #include "abd_wide.hpp"
 #include "dist_host.hpp"
 #include "table_selftest.hpp"
+#include "rehash_selftest.hpp"
 
 namespace sr {
 
@@ -1307,6 +1308,29 @@ int32_t sr_selftest_table_growth(void) {
         set_error(x.what());
         return SR_ERR_ARG;
     }
+}
+
+int32_t sr_selftest_rehash_gpu(int32_t device) {
+    try {
+        std::string why;
+        if (!rehash_test::run_all(device, why, device < 0)) {
+            set_error(why);
+            return SR_ERR_ARG;
+        }
+        return SR_OK;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int32_t sr_gpu_bfs_table_audit(const sr_bfs* b, sr_table_audit* out, uint32_t size) {
+    if (!b || (!out && size)) return SR_ERR_ARG;
+    if (out) std::memcpy(out, &b->e->audit, std::min<size_t>(size, sizeof(sr_table_audit)));
+    return (int32_t)sizeof(sr_table_audit);
 }
 
 int32_t sr_table_encoding(int32_t words, int32_t key_bits, uint64_t slots, uint32_t* out) {

@@ -24,6 +24,7 @@
 #include "../../include/stateright_gpu.h"
 #include "device.hpp"
 #include "kernels.hpp"
+#include "kernels_audit.hpp"
 #include "live.hpp"
 
 namespace sr {
@@ -115,6 +116,7 @@ class EngineBase {
     int status = SR_OK;
     std::string error;
     sr_stats stats{};
+    sr_table_audit audit{};  // the visited-set audit of a counting run (kernels_audit.hpp); ran = 0 otherwise
     std::vector<DiscoveryRec> disc;
     std::vector<double> launch_ms;    // per timed launch (profile=1), in launch order
     std::vector<u64> launch_frontier; // the frontier each launch expanded (0 if unknown)
@@ -477,6 +479,7 @@ class Engine final : public EngineBase {
                 if (e.code != SR_ERR_CAPACITY || attempt >= 3) throw;
                 if (o_.verbose) std::fprintf(stderr, "[sr] %s; restarting with larger buffers\n", e.what());
                 pessimistic_ = true;
+                restarts_++;
                 grow_factor_ *= 4;
                 (void)stream_sync(stream_);
                 rehash_pending_ = false;  // (a failed enqueued rehash is this restart's cause, or moot)
@@ -685,31 +688,23 @@ class Engine final : public EngineBase {
     // SR_REHASH_RANGES=0 (measurement knob) always takes the latter.
     void launch_rehash(const TableView& from, u64 old_cap, u64 f) {
         const u64 cap = old_cap * f;
-        const TableView to0 = make_table_view(m_, nullptr, nullptr, cap);
-        u32 lg = 0;
-        while ((1ull << lg) < f) ++lg;
-        const u64 S = to0.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
-        const bool ranges = rehash_ranges_ && !from.meta && rehash_by_ranges(from, to0, lg, cap);
-        alloc_table(cap, !ranges);
-        table_unzeroed_ = ranges;
-        SR_HIP(hipMemsetAsync(aux_.p, 0, sizeof(u32), stream_));
-        if (ranges) {
-            const u64 nranges = cap / S, spill_cap = nranges + 65536;
-            if (spill_.n < spill_cap + 1) spill_.alloc(o_.device, spill_cap + 1);
-            SR_HIP(hipMemsetAsync(spill_.p, 0, sizeof(u64), stream_));
-            if (to0.s32)
-                rehash_ranges<u32><<<(u32)nranges, REBUILD_BLOCK, 0, stream_>>>(from, old_cap, view(), lg, spill_.p,
-                                                                               spill_cap, aux_.p);
-            else
-                rehash_ranges<u64><<<(u32)nranges, REBUILD_BLOCK, 0, stream_>>>(from, old_cap, view(), lg, spill_.p,
-                                                                               spill_cap, aux_.p);
-            SR_HIP(hipGetLastError());
-            rehash_spill<<<256, 256, 0, stream_>>>(from, view(), spill_.p, spill_cap, aux_.p);
-        } else {
-            rehash<<<blocks_for(old_cap, 256), 256, 0, stream_>>>(from, old_cap, view(), aux_.p);
-        }
-        SR_HIP(hipGetLastError());
+        sr::launch_rehash(
+            from, old_cap, make_table_view(m_, nullptr, nullptr, cap), cap, rehash_ranges_,
+            [&](bool ranges) {
+                alloc_table(cap, !ranges);
+                table_unzeroed_ = ranges;
+                SR_HIP(hipMemsetAsync(aux_.p, 0, sizeof(u32), stream_));
+                return view();
+            },
+            spill_, o_.device, aux_.p, stream_);
+        // SR_REHASH_FAIL=k (tests): the k-th growth of this check reports a full table, by a store
+        // to its error word enqueued behind the rehash; the new table itself is complete
+        if (++growths_ == rehash_fail_) SR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(aux_.p), (int)ERR_TABLE_FULL, 1, stream_));
     }
+    u32 table0_log2_ = std::getenv("SR_TABLE_LOG2") ? (u32)std::min(22, std::max(10, std::atoi(std::getenv("SR_TABLE_LOG2")))) : 22u;
+    u64 growths_ = 0;  // rehashes launched by this check, restarts included
+    u32 restarts_ = 0;  // capacity restarts of this check (sr_stats.restarts)
+    u64 rehash_fail_ = std::getenv("SR_REHASH_FAIL") ? (u64)std::atoll(std::getenv("SR_REHASH_FAIL")) : 0u;
     bool rehash_ranges_ = !std::getenv("SR_REHASH_RANGES") || std::atoi(std::getenv("SR_REHASH_RANGES")) != 0;
     DBuf<u64> spill_;  // rehash_ranges' spill list: [0] count, then old slot indices
     // The visited set was built by rehash_ranges (allocated without a clear): released without one
@@ -780,6 +775,29 @@ class Engine final : public EngineBase {
         SR_HIP(hipMemcpyAsync(&d, aux_.p + 1, sizeof(u32), hipMemcpyDeviceToHost, stream_));
         SR_HIP(stream_sync(stream_));
         stats.max_displacement = d;
+    }
+
+    // The visited-set audit (kernels_audit.hpp) of the final table against the arena's
+    // lstart_.back() states; a measurement pass like the scan above (sr_opts.counters).
+    void table_audit() {
+        if (!o_.counters || !cap_ || !keys_.p) return;
+        const u64 n = lstart_.back();
+        DBuf<u64> acc, ls;
+        DBuf<u32> marks;
+        acc.alloc(o_.device, sizeof(AuditCounters) / 8);
+        ls.alloc(o_.device, lstart_.size());
+        marks.alloc(o_.device, (size_t)((cap_ + 31) / 32));
+        SR_HIP(hipMemsetAsync(acc.p, 0, sizeof(AuditCounters), stream_));
+        SR_HIP(hipMemcpyAsync(ls.p, lstart_.data(), lstart_.size() * sizeof(u64), hipMemcpyHostToDevice, stream_));
+        AuditCounters* a = reinterpret_cast<AuditCounters*>(acc.p);
+        launch_audit_table(view(), cap_, marks.p, a, stream_);
+        launch_audit_arena(m_, view(), arena_.p, fifo_ ? apar_.p : nullptr, n, ls.p, (u32)lstart_.size() - 1, A_, marks.p, a,
+                           stream_);
+        AuditCounters h{};
+        SR_HIP(hipMemcpyAsync(&h, acc.p, sizeof(h), hipMemcpyDeviceToHost, stream_));
+        SR_HIP(stream_sync(stream_));
+        audit = sr_table_audit{1u, fifo_ ? 1u : 0u, cap_, h.occupied, h.misplaced, h.duplicates, h.arena_states,
+                               h.arena_missing, h.arena_shared, h.meta_wrong};
     }
 
     // The BFS-tree arena holds every level's states (visit order) and their parent ranks; grows
@@ -993,6 +1011,8 @@ class Engine final : public EngineBase {
         stats = sr_stats{};
         stats.words_per_state = W;
         stats.order_used = (u32)order;
+        stats.restarts = restarts_;
+        audit = sr_table_audit{};
         launch_ms.clear();
         launch_frontier.clear();
         launch_probes.clear();
@@ -1002,7 +1022,8 @@ class Engine final : public EngineBase {
         // Visited set sized for <= table_load_ load at the hinted unique count.
         // (without a hint: 2^22 slots, 32 MiB, a few us to clear and recycled between checks; the
         // table then grows in steps of SR_GROW_STEP)
-        u64 cap = std::max<u64>((u64)(1u << 22) * grow_factor_, min_table_cap(m_));
+        // SR_TABLE_LOG2 (tests, 10..22): a smaller first table, so that a small model grows it
+        u64 cap = std::max<u64>((1ull << table0_log2_) * grow_factor_, min_table_cap(m_));
         // Hints beyond 2^31 states (increment_lock N=12: 5.2e9) size the table for <= 0.75 load and
         // the arena with 30% slack, so that table + arena fit one MI355X's 288 GB.
         const bool huge = o_.capacity_hint > (1ull << 31);
@@ -1207,6 +1228,7 @@ class Engine final : public EngineBase {
         auto t_end = Clock::now();
         collect_timing();
         displacement_stats();
+        table_audit();
         stats.level_loop_sec = secs(t_loop, t_end);
         stats.total_sec = secs(t_start, t_end);
         stats.table_capacity = cap_;

@@ -2236,6 +2236,41 @@ template <int = 0> __global__ void remap_slots(u32* cand, u64 n, TableView from,
     cand[i] = (u32)find_slot(to, reprobe(from, to, s, slot_load(from, s)));
 }
 
+// Host: enqueues on `s` the growth of table `from` (old_cap slots) into one of `cap` slots, for
+// every caller (the one-GPU engine, the partitioned engine, the rehash self-test): range by range
+// without a clear (rehash_ranges + rehash_spill) when allow_ranges, no meta moves along and
+// rehash_by_ranges says the new homes of a range of old homes are a range; else one CAS insertion
+// per entry into a zeroed table (rehash). alloc_to(ranges) allocates the new table and returns its
+// view (natural or as the caller's tables are: the probe limit is taken from it), zeroed on `s`
+// unless `ranges`: rehash_ranges writes every slot. Error bits are OR-ed into *err (the caller
+// clears it). spill: the spill list, (re)allocated here; spill_cap 0 sizes it for every range
+// spilling once plus 65536 (tests pass a smaller one). Returns whether it went by ranges.
+template <class AllocTo>
+inline bool launch_rehash(const TableView& from, u64 old_cap, const TableView& to0, u64 cap, bool allow_ranges,
+                          AllocTo&& alloc_to, DBuf<u64>& spill, int device, u32* err, hipStream_t s, u64 spill_cap = 0) {
+    u32 lg = 0;
+    while ((old_cap << lg) < cap) ++lg;
+    const u64 S = to0.s32 ? rebuild_slots<u32>() : rebuild_slots<u64>();
+    const bool ranges = allow_ranges && !from.meta && rehash_by_ranges(from, to0, lg, cap);
+    const TableView to = alloc_to(ranges);
+    if (ranges) {
+        const u64 nranges = cap / S;
+        if (!spill_cap) spill_cap = nranges + 65536;
+        if (spill.n < spill_cap + 1) spill.alloc(device, spill_cap + 1);
+        SR_HIP(hipMemsetAsync(spill.p, 0, sizeof(u64), s));
+        if (to0.s32)
+            rehash_ranges<u32><<<(u32)nranges, REBUILD_BLOCK, 0, s>>>(from, old_cap, to, lg, spill.p, spill_cap, err);
+        else
+            rehash_ranges<u64><<<(u32)nranges, REBUILD_BLOCK, 0, s>>>(from, old_cap, to, lg, spill.p, spill_cap, err);
+        SR_HIP(hipGetLastError());
+        rehash_spill<<<256, 256, 0, s>>>(from, to, spill.p, spill_cap, err);
+    } else {
+        rehash<<<(u32)((old_cap + 255) / 256), 256, 0, s>>>(from, old_cap, to, err);
+    }
+    SR_HIP(hipGetLastError());
+    return ranges;
+}
+
 // ---- exclusive scan of u32 counts (3-phase: tile sums, scan of sums, tile scan + carry) ----
 constexpr int SCAN_BLOCK = 256;
 constexpr int SCAN_ITEMS = 8;

@@ -19,8 +19,20 @@ def test_header_declares_entry_points():
     names = declared_functions()
     for must in ("sr_gpu_bfs_spawn", "sr_gpu_bfs_join", "sr_gpu_bfs_is_done", "sr_gpu_bfs_state_count",
                  "sr_gpu_bfs_unique_state_count", "sr_gpu_bfs_max_depth", "sr_gpu_bfs_discovery",
-                 "sr_gpu_bfs_free"):
+                 "sr_gpu_bfs_free", "sr_gpu_bfs_table_audit", "sr_selftest_rehash_gpu"):
         assert must in names
+
+
+def test_table_audit_mirror_matches_the_header():
+    # sr_table_audit: 72 bytes as documented, the mirror lists the header's fields in order, and the
+    # sized call reports the engine's size without a checker's data being touched
+    from stateright_amd import _native
+    text = open(HEADER).read()
+    body = text[text.index("typedef struct sr_table_audit {"):text.index("} sr_table_audit;")]
+    fields = re.findall(r"\b(?:uint64_t|uint32_t)\s+([a-z0-9_]+);", body)
+    assert fields == [n for n, _ in _native.sr_table_audit._fields_]
+    assert ctypes.sizeof(_native.sr_table_audit) == 72
+    assert _native.load().sr_gpu_bfs_table_audit(None, None, 0) < 0  # SR_ERR_ARG: no checker
 
 
 def test_library_exports_every_declared_symbol():

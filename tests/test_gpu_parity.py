@@ -11,6 +11,7 @@ import os
 
 import pytest
 
+from audit_lib import assert_clean_audit
 from oracle_lib import (BINARY_CLOCK, INCREMENT, INCREMENT_LOCK, LINEAR_EQUATION, PAXOS, TWO_PHASE, OracleRun,
                         replay)
 from paxos_golden import PAXOS_VALUE_CHOSEN_PATH
@@ -237,6 +238,11 @@ def test_increment_lock_quotient_table_grows(order):
     c = sr.IncrementLock(n).checker().order(order).spawn_bfs().join()
     assert (c.unique_state_count(), c.state_count(), c.max_depth()) == (o.unique_state_count, o.state_count, o.max_depth)
     assert c.stats()["rehashes"] > 0
+    # ... and the grown table holds exactly the arena's states (a counting run audits it)
+    c = sr.IncrementLock(n).checker().order(order).counters().spawn_bfs().join()
+    assert (c.unique_state_count(), c.state_count(), c.max_depth()) == (o.unique_state_count, o.state_count, o.max_depth)
+    assert c.stats()["rehashes"] > 0
+    assert_clean_audit(c, fifo=order == "fifo")
 
 
 def test_increment_lock_grows_through_x5_levels():
@@ -246,10 +252,12 @@ def test_increment_lock_grows_through_x5_levels():
     # table, not overfill a small quotient table (kernels.hpp SlotWork.room); counts stay exact.
     n = 10
     expect = 1 + 4 * sum(math.factorial(n) // math.factorial(n - k) for k in range(1, n + 1))
-    c = sr.IncrementLock(n).checker().order("fast").spawn_bfs().join()
-    assert c.unique_state_count() == c.state_count() == expect
-    assert c.max_depth() == 4 * n
-    assert c.stats()["rehashes"] > 0
+    for counters in (False, True):
+        c = sr.IncrementLock(n).checker().order("fast").counters(counters).spawn_bfs().join()
+        assert c.unique_state_count() == c.state_count() == expect
+        assert c.max_depth() == 4 * n
+        assert c.stats()["rehashes"] > 0
+    assert_clean_audit(c, fifo=False)
 
 
 def test_2pc_10_fifo_matches_fast():
@@ -274,10 +282,12 @@ def test_growth_from_small_table(step, monkeypatch):
     # counts stay exact.
     monkeypatch.setenv("SR_GROW_STEP", step)
     n = 9
-    c = sr.TwoPhaseSys(n).checker().order("fast").spawn_bfs().join()
-    assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
-    assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
-    assert c.stats()["rehashes"] >= (2 if step == "2" else 1)
+    for counters in (False, True):
+        c = sr.TwoPhaseSys(n).checker().order("fast").counters(counters).spawn_bfs().join()
+        assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
+        assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
+        assert c.stats()["rehashes"] >= (2 if step == "2" else 1)
+    assert_clean_audit(c, fifo=False)
 
 
 @pytest.mark.parametrize("ranges", ["0", "1"])
@@ -290,15 +300,19 @@ def test_rehash_by_ranges(step, ranges, monkeypatch):
     monkeypatch.setenv("SR_GROW_STEP", step)
     monkeypatch.setenv("SR_REHASH_RANGES", ranges)
     n = 9
-    c = sr.TwoPhaseSys(n).checker().order("fast").spawn_bfs().join()
-    assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
-    assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
-    assert c.stats()["rehashes"] >= 1
+    for counters in (False, True):
+        c = sr.TwoPhaseSys(n).checker().order("fast").counters(counters).spawn_bfs().join()
+        assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
+        assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
+        assert c.stats()["rehashes"] >= 1
+    assert_clean_audit(c, fifo=False)
     expect = 1 + 4 * sum(math.factorial(n) // math.factorial(n - k) for k in range(1, n + 1))
-    c = sr.IncrementLock(n).checker().order("fast").spawn_bfs().join()
-    assert c.unique_state_count() == c.state_count() == expect
-    assert c.max_depth() == 4 * n
-    assert c.stats()["rehashes"] >= 1
+    for counters in (False, True):
+        c = sr.IncrementLock(n).checker().order("fast").counters(counters).spawn_bfs().join()
+        assert c.unique_state_count() == c.state_count() == expect
+        assert c.max_depth() == 4 * n
+        assert c.stats()["rehashes"] >= 1
+    assert_clean_audit(c, fifo=False)
 
 
 def test_rehash_by_ranges_probe_limit(monkeypatch):
@@ -307,9 +321,11 @@ def test_rehash_by_ranges_probe_limit(monkeypatch):
     monkeypatch.setenv("SR_DISP_LIMIT", "6")
     monkeypatch.setenv("SR_GROW_STEP", "2")
     n = 7
-    c = sr.TwoPhaseSys(n).checker().order("fast").spawn_bfs().join()
-    assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
-    assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
+    for counters in (False, True):
+        c = sr.TwoPhaseSys(n).checker().order("fast").counters(counters).spawn_bfs().join()
+        assert c.unique_state_count() == 6 ** n + 4 ** n + 2 ** n
+        assert 3 * c.state_count() == 4 * n * 6 ** n + 3 * (n + 1) * 4 ** n + 3 * n * 2 ** n + 6
+    assert_clean_audit(c, fifo=False)
 
 
 def test_paxos_golden():
@@ -397,6 +413,7 @@ def test_probe_limit_overflow_doubles_the_table(case, order, pipe, monkeypatch):
     st = c.stats()
     assert st["table_doublings"] > 0 and st["restarts"] == 0
     assert st["displacement_limit"] == limit and 0 < st["max_displacement"] < limit
+    assert_clean_audit(c, fifo=order == "fifo")
 
 
 def test_displacement_stats_increment_lock_10():

@@ -17,6 +17,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pybfs  # noqa: E402
+from audit_lib import assert_clean_audit  # noqa: E402
 from stateright_amd import StateRecorder  # noqa: E402
 from stateright_amd import _native as N  # noqa: E402
 from stateright_amd.models import Spread  # noqa: E402
@@ -88,8 +89,8 @@ def check_encoding(c, words, bits, want):
     assert e["dbits"] == ((32 if s32 else 64) - qbits if qbits else 0)
 
 
-def run(words, bits, loops, order, free_bits=F, mark=MARK, record=True, partitions=1):
-    b = Spread(words, bits, free_bits, loops, mark).checker().order(order)
+def run(words, bits, loops, order, free_bits=F, mark=MARK, record=True, partitions=1, counters=False):
+    b = Spread(words, bits, free_bits, loops, mark).checker().order(order).counters(counters)
     rec = None
     if record:
         rec = StateRecorder()
@@ -166,12 +167,12 @@ GROWTH = [
 ]
 
 
-def check_growth(words, bits, step, kind, order, monkeypatch):
+def check_growth(words, bits, step, kind, order, monkeypatch, counters=False):
     if step is None:
         monkeypatch.delenv("SR_GROW_STEP", raising=False)
     else:
         monkeypatch.setenv("SR_GROW_STEP", step)
-    c, _ = run(words, bits, 0, order, free_bits=GF, mark=GMARK, record=False)
+    c, _ = run(words, bits, 0, order, free_bits=GF, mark=GMARK, record=False, counters=counters)
     assert (c.unique_state_count(), c.state_count(), c.max_depth()) == closed_form(GF, 0)
     path = c.discovery("marked")
     assert len(path) == bin(GMARK).count("1") and path.last_state() == pybfs.spread_describe(words, bits, GF, GMARK)
@@ -196,6 +197,8 @@ def check_growth(words, bits, step, kind, order, monkeypatch):
         assert first["qbits"] == bits - DEFAULT_LOG2 and last["qbits"] == max(1, bits - cap.bit_length() + 1), (first, last)
     else:
         assert first["qbits"] == 0 and last["qbits"] == 0
+    if counters:  # the grown table holds exactly the arena's states
+        assert_clean_audit(c, fifo=order == "fifo")
     return c
 
 
@@ -204,6 +207,7 @@ def check_growth(words, bits, step, kind, order, monkeypatch):
 def test_growth(words, bits, step, kind, ranges, monkeypatch):
     monkeypatch.setenv("SR_REHASH_RANGES", ranges)
     check_growth(words, bits, step, kind, "fast", monkeypatch)
+    check_growth(words, bits, step, kind, "fast", monkeypatch, counters=True)
 
 
 def test_growth_fifo_two_word_key_below_its_key_space(monkeypatch):
@@ -216,6 +220,7 @@ def test_growth_fifo_two_word_key_below_its_key_space(monkeypatch):
     # more than about that many states at any size, and such a check ends with SR_ERR_CAPACITY. See
     # DESIGN.md "Which encoding, as tested".)
     check_growth(2, 24, None, "quotient", "fifo", monkeypatch)
+    check_growth(2, 24, None, "quotient", "fifo", monkeypatch, counters=True)
 
 
 # ---- partitioned engine ----
@@ -257,8 +262,13 @@ def part_tables(st, parts):
 @pytest.mark.parametrize("words,bits", [(1, 39), (1, 45), (2, 60), (2, 18), (4, 50)])
 def test_partitioned_growth(words, bits, monkeypatch):
     monkeypatch.setenv("SR_HEAD_MAX", "0")
+    check_partitioned_growth(words, bits, False)
+    assert_clean_audit(check_partitioned_growth(words, bits, True), fifo=False)
+
+
+def check_partitioned_growth(words, bits, counters):
     b = Spread(words, bits, 17, 0, 0b01011001101001011).checker().order("fast").partitions(2).capacity_hint(30000)
-    c = b.spawn_bfs().join()
+    c = b.counters(counters).spawn_bfs().join()
     c.assert_properties()
     assert (c.unique_state_count(), c.state_count(), c.max_depth()) == closed_form(17, 0)
     path = c.discovery("marked")
@@ -271,6 +281,7 @@ def test_partitioned_growth(words, bits, monkeypatch):
     assert ran_with(st)[:2] == (last["qbits"], last["s32"]) and st["displacement_limit"] == last["plimit"], (st, last)
     if (words, bits) == (1, 39):
         assert (first["s32"], last["s32"]) == (0, 1)
+    return c
 
 
 # Part tables that MUST grow across their key space, by load alone: two partitions of an unhinted
@@ -281,11 +292,13 @@ def test_partitioned_growth(words, bits, monkeypatch):
 @pytest.mark.parametrize("words", [1, 2])
 def test_partitioned_growth_across_the_key_space(words):
     bits, free_bits, mark = 24, 23, 0b01011001101001011001101
-    c, _ = run(words, bits, 0, "fast", free_bits=free_bits, mark=mark, record=False, partitions=2)
-    assert (c.unique_state_count(), c.state_count(), c.max_depth()) == closed_form(free_bits, 0)
-    path = c.discovery("marked")
-    assert len(path) == bin(mark).count("1") and c.replay(path.action_ids)[0] == path.states
-    st = c.stats()
-    k = part_tables(st, 2)
-    assert st["rehashes"] >= 1 and k >= bits, st
-    assert N.table_encoding(words, bits, 1 << 23)["qbits"] == 1 and ran_with(st)[:2] == (1, 1 if words == 1 else 0), st
+    for counters in (False, True):
+        c, _ = run(words, bits, 0, "fast", free_bits=free_bits, mark=mark, record=False, partitions=2, counters=counters)
+        assert (c.unique_state_count(), c.state_count(), c.max_depth()) == closed_form(free_bits, 0)
+        path = c.discovery("marked")
+        assert len(path) == bin(mark).count("1") and c.replay(path.action_ids)[0] == path.states
+        st = c.stats()
+        k = part_tables(st, 2)
+        assert st["rehashes"] >= 1 and k >= bits, st
+        assert N.table_encoding(words, bits, 1 << 23)["qbits"] == 1 and ran_with(st)[:2] == (1, 1 if words == 1 else 0), st
+    assert_clean_audit(c, fifo=False)

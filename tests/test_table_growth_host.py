@@ -17,6 +17,20 @@ def test_table_growth_selftest():
     assert N.load().sr_selftest_table_growth() == 0, N.last_error()
 
 
+def test_rehash_selftest_cases_on_the_host():
+    # The GPU self-test of the rehash kernels (csrc/rehash_selftest.hpp) with device < 0: every case
+    # is built and its expectations come from the host model alone, nothing is launched. The random
+    # fills must be predicted to spill, the long run to extend its window at least twice, the
+    # constructed spills to have their exact counts, and B = 35 at 2^12 slots to be a pair of slot widths.
+    assert N.load().sr_selftest_rehash_gpu(-1) == 0, N.last_error()
+
+
+def test_78_bit_key_cannot_grow_from_a_small_table():
+    # why tests/test_gpu_table_audit.py grows the 78-bit key at F = 22: its smallest table is 2^22 slots
+    assert enc(2, 78, 1 << 22)["min_cap_log2"] == 22 and all(enc(w, b, 1 << 12)["min_cap_log2"] <= 12
+                                                             for w, b in ((1, 24), (1, 44), (2, 50), (4, 50)))
+
+
 @pytest.mark.parametrize("words,bits", [(2, 18), (2, 24), (4, 18), (2, 2), (2, 50), (2, 90)])
 def test_multi_word_mode_is_fixed_across_the_key_space(words, bits):
     # a multi-word key stays in quotient mode when the table passes its key space (1-bit remainder,
