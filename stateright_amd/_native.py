@@ -76,10 +76,17 @@ class sr_live_result(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-class sr_live_weak(ctypes.Structure):
-    _fields_ = [
+class _LiveFairStats(ctypes.Structure):
+    """sr_live_weak and sr_live_strong: one layout, but for the second field (reserved0 / levels)."""
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+def _live_fair_fields(second):
+    return [
         ("ran", ctypes.c_int32),
-        ("reserved0", ctypes.c_int32),
+        second,
         ("cyclic_states", ctypes.c_uint64),
         ("components", ctypes.c_uint64),
         ("fair_components", ctypes.c_uint64),
@@ -94,30 +101,13 @@ class sr_live_weak(ctypes.Structure):
         ("pass_ms", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+class sr_live_weak(_LiveFairStats):
+    _fields_ = _live_fair_fields(("reserved0", ctypes.c_int32))
 
 
-class sr_live_strong(ctypes.Structure):
-    _fields_ = [
-        ("ran", ctypes.c_int32),
-        ("levels", ctypes.c_uint32),
-        ("cyclic_states", ctypes.c_uint64),
-        ("components", ctypes.c_uint64),
-        ("fair_components", ctypes.c_uint64),
-        ("goal_states", ctypes.c_uint64),
-        ("fair_states", ctypes.c_uint64),
-        ("stem_len", ctypes.c_int64),
-        ("loop_len", ctypes.c_int64),
-        ("scc_rounds", ctypes.c_uint32),
-        ("reach_rounds", ctypes.c_uint32),
-        ("segments", ctypes.c_uint32),
-        ("reserved1", ctypes.c_uint32),
-        ("pass_ms", ctypes.c_double),
-    ]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+class sr_live_strong(_LiveFairStats):
+    _fields_ = _live_fair_fields(("levels", ctypes.c_uint32))
 
 
 class sr_sim_opts(ctypes.Structure):
@@ -497,6 +487,28 @@ def host_graph(model_id, params, max_states=1 << 22):
     return succ, inits, conds
 
 
+def _liveness_host(name, call, stats=None):
+    """Behind the liveness_host* functions: call(res, acts, cap) is the entry point `name`; the witness' buffer
+    grows until it fits. The dict of sr_live_result plus `unique` and `actions`; stats = (key, struct) adds the
+    mode's counters."""
+    res = sr_live_result()
+    cap = 1 << 16
+    while True:
+        acts = (ctypes.c_int64 * cap)()
+        n = call(ctypes.byref(res), acts, cap)
+        if n < 0:
+            raise ValueError(f"{name}: {last_error()} (status {n})")
+        if res.witness_len <= cap:
+            break
+        cap = res.witness_len
+    out = res.as_dict()
+    out["unique"] = n
+    out["actions"] = list(acts[:max(0, res.witness_len)])
+    if stats:
+        out[stats[0]] = stats[1].as_dict()
+    return out
+
+
 def liveness_host(model_id, params, prop=0, max_states=1 << 22, fairness=0):
     """The complete `eventually` check of a registered model on the host (csrc/live.hpp; no device
     needed): a host search over at most `max_states` states, the fixpoint and the deterministic
@@ -506,20 +518,17 @@ def liveness_host(model_id, params, prop=0, max_states=1 << 22, fairness=0):
     lib = load()
     params = list(params)
     arr = (ctypes.c_int64 * max(1, len(params)))(*params)
-    res = sr_live_result()
-    cap = 1 << 16
-    while True:
-        acts = (ctypes.c_int64 * cap)()
-        n = lib.sr_liveness_host_fair(model_id, arr, len(params), prop, fairness, max_states, ctypes.byref(res), acts, cap)
-        if n < 0:
-            raise ValueError(f"sr_liveness_host: {last_error()} (status {n})")
-        if res.witness_len <= cap:
-            break
-        cap = res.witness_len
-    out = res.as_dict()
-    out["unique"] = n
-    out["actions"] = list(acts[:max(0, res.witness_len)])
-    return out
+    return _liveness_host("sr_liveness_host", lambda res, acts, cap: lib.sr_liveness_host_fair(
+        model_id, arr, len(params), prop, fairness, max_states, res, acts, cap))
+
+
+def _liveness_host_fair(mode, stats, model_id, params, prop, max_states):
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    entry = getattr(lib, "sr_liveness_host_" + mode)
+    return _liveness_host("sr_liveness_host_" + mode, lambda res, acts, cap: entry(
+        model_id, arr, len(params), prop, max_states, res, ctypes.byref(stats), acts, cap), (mode, stats))
 
 
 def liveness_host_weak(model_id, params, prop=0, max_states=1 << 22):
@@ -528,24 +537,7 @@ def liveness_host_weak(model_id, params, prop=0, max_states=1 << 22):
     components, fair_components, goal_states, fair_states, stem_len, loop_len, ...). The witness'
     `actions` are the stem's followed by the closed walk's; ValueError (status -4) for a model whose
     slots are not fairness classes."""
-    lib = load()
-    params = list(params)
-    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
-    res, weak = sr_live_result(), sr_live_weak()
-    cap = 1 << 16
-    while True:
-        acts = (ctypes.c_int64 * cap)()
-        n = lib.sr_liveness_host_weak(model_id, arr, len(params), prop, max_states, ctypes.byref(res), ctypes.byref(weak), acts, cap)
-        if n < 0:
-            raise ValueError(f"sr_liveness_host_weak: {last_error()} (status {n})")
-        if res.witness_len <= cap:
-            break
-        cap = res.witness_len
-    out = res.as_dict()
-    out["unique"] = n
-    out["actions"] = list(acts[:max(0, res.witness_len)])
-    out["weak"] = weak.as_dict()
-    return out
+    return _liveness_host_fair("weak", sr_live_weak(), model_id, params, prop, max_states)
 
 
 def liveness_host_strong(model_id, params, prop=0, max_states=1 << 22):
@@ -554,24 +546,7 @@ def liveness_host_strong(model_id, params, prop=0, max_states=1 << 22):
     cyclic_states, components, fair_components, goal_states, fair_states, stem_len, loop_len, ...). The
     witness' `actions` are the stem's followed by the closed walk's; ValueError (status -4) for a model whose
     slots are not fairness classes."""
-    lib = load()
-    params = list(params)
-    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
-    res, strong = sr_live_result(), sr_live_strong()
-    cap = 1 << 16
-    while True:
-        acts = (ctypes.c_int64 * cap)()
-        n = lib.sr_liveness_host_strong(model_id, arr, len(params), prop, max_states, ctypes.byref(res), ctypes.byref(strong), acts, cap)
-        if n < 0:
-            raise ValueError(f"sr_liveness_host_strong: {last_error()} (status {n})")
-        if res.witness_len <= cap:
-            break
-        cap = res.witness_len
-    out = res.as_dict()
-    out["unique"] = n
-    out["actions"] = list(acts[:max(0, res.witness_len)])
-    out["strong"] = strong.as_dict()
-    return out
+    return _liveness_host_fair("strong", sr_live_strong(), model_id, params, prop, max_states)
 
 
 def runtime_versions():

@@ -621,20 +621,14 @@ class GpuBfsChecker:
         if st != 0:
             raise CheckerError("sr_gpu_bfs_liveness", st)
         out = r.as_dict()
-        if getattr(self, "_weak", False) and r.ran:
-            w = N.sr_live_weak()
-            st = self._lib.sr_gpu_bfs_liveness_weak(self._h, self._prop_index(name), ctypes.byref(w))
-            if st != 0:
-                raise CheckerError("sr_gpu_bfs_liveness_weak", st)
-            if w.ran:
-                out["weak"] = w.as_dict()
-        if getattr(self, "_strong", False) and r.ran:
-            g = N.sr_live_strong()
-            st = self._lib.sr_gpu_bfs_liveness_strong(self._h, self._prop_index(name), ctypes.byref(g))
-            if st != 0:
-                raise CheckerError("sr_gpu_bfs_liveness_strong", st)
-            if g.ran:
-                out["strong"] = g.as_dict()
+        for mode, stats in (("weak", N.sr_live_weak), ("strong", N.sr_live_strong)):
+            if getattr(self, "_" + mode, False) and r.ran:
+                s = stats()
+                st = getattr(self._lib, "sr_gpu_bfs_liveness_" + mode)(self._h, self._prop_index(name), ctypes.byref(s))
+                if st != 0:
+                    raise CheckerError("sr_gpu_bfs_liveness_" + mode, st)
+                if s.ran:
+                    out[mode] = s.as_dict()
         return out
 
     def loop_start(self, name):
@@ -786,14 +780,11 @@ class GpuBfsChecker:
                 if loops:
                     states, _ = self.replay(actions, init)
                     closed = states[-1] in states[:-1]
-                    if closed and getattr(self, "_weak", False):  # (weak fairness: only a weakly fair loop refutes)
-                        closed = self._loop_is_fair(actions, init, states.index(states[-1]))
-                        if not closed:
-                            info.append("incorrect counterexample closes a loop that is not weakly fair")
-                    if closed and getattr(self, "_strong", False):  # (strong fairness: only a strongly fair loop)
-                        closed = self._loop_is_fair(actions, init, states.index(states[-1]), strong=True)
-                        if not closed:
-                            info.append("incorrect counterexample closes a loop that is not strongly fair")
+                    for mode, how in (("_weak", "weakly"), ("_strong", "strongly")):  # (only a loop that is fair so refutes)
+                        if closed and getattr(self, mode, False):
+                            closed = self._loop_is_fair(actions, init, states.index(states[-1]), strong=mode == "_strong")
+                            if not closed:
+                                info.append(f"incorrect counterexample closes a loop that is not {how} fair")
                 if not terminal and not closed and self._accepts_stutter_ends():
                     closed = self._sink_kind(actions, init) == N.SR_LIVE_END_STUTTER
                 if not satisfied and (terminal or closed):

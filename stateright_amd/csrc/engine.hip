@@ -502,6 +502,61 @@ static i64 describe_roundtrip(const M& m, i64 max_states, std::string& why) {
         return (i64)std::min<size_t>(queue.size(), (size_t)max_states);
     }
 }
+
+// Behind the three sr_liveness_host* entry points (`name`). args: nullptr, or what is wrong with the arguments;
+// fairness: nullptr, or the mode ("weak fairness") that needs a FAIR_SLOTS model; form(m, moves) runs the host
+// form (live.hpp) on a model with an `eventually` property and returns its LiveHost.
+template <class Form>
+static int64_t liveness_host_entry(const char* name, const char* args, const char* fairness, int32_t model, const int64_t* p, int32_t np,
+                                   sr_live_result* out, int64_t* action_ids, int32_t cap, Form&& form) {
+    try {
+        if (args) throw Error(SR_ERR_ARG, args);
+        // SR_LIVE_MOVES=0: the progress mode and the fair ones compare states even where the model's
+        // `enabled_moves` names its self-loops (tests run both and compare; read per call)
+        const char* e = std::getenv("SR_LIVE_MOVES");
+        const bool moves = !e || std::atoi(e) != 0;
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            if constexpr (has_emask<M>::value) {
+                const LiveHost h = form(m, moves);
+                *out = h.r;
+                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
+                return (i64)h.unique;
+            } else {
+                if (fairness && !fair_slots_model<M>)
+                    throw Error(SR_ERR_UNSUPPORTED, std::string(fairness) + ": this model's slots are not fairness classes");
+                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
+            }
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error(std::string(name) + ": model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+// A fair host form's LiveHostFair: the mode's counters go to *stats, the rest to liveness_host_entry.
+template <class Stats>
+static LiveHost live_host_split(LiveHostFair<Stats> f, Stats* stats) {
+    *stats = f.s;
+    return std::move(f.h);
+}
+
+// Behind sr_gpu_bfs_loop_fair and sr_gpu_bfs_loop_strongly_fair.
+static int32_t loop_fair_entry(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t loop_start, bool strong) {
+    if (!b || !b->e->finished.load(std::memory_order_acquire) || n < 0 || (n > 0 && !ids) || loop_start < 0 || loop_start > n) return -1;
+    try {
+        return b->e->loop_fair(init, ids, n, loop_start, strong);
+    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
+        set_error(x.what());
+        return -1;
+    }
+}
+
 }  // namespace sr
 
 extern "C" {
@@ -687,35 +742,14 @@ int32_t sr_gpu_bfs_sink_kind(const sr_bfs* b, int32_t init, const int64_t* ids, 
 
 int64_t sr_liveness_host_fair(int32_t model, const int64_t* p, int32_t np, int32_t prop, int32_t fairness, int64_t max_states,
                               sr_live_result* out, int64_t* action_ids, int32_t cap) {
-    try {
-        if (!out || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host: out and max_states >= 1");
-        if (fairness != 0 && fairness != 1) throw Error(SR_ERR_ARG, "sr_liveness_host_fair: fairness must be 0 (none) or 1 (progress)");
-        // SR_LIVE_MOVES=0: the progress mode compares states even where the model's `enabled_moves` names
-        // its self-loops (tests run both and compare; read per call)
-        const char* e = std::getenv("SR_LIVE_MOVES");
-        const bool moves = !e || std::atoi(e) != 0;
-        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
-            using M = std::decay_t<decltype(m)>;
-            if constexpr (has_emask<M>::value) {
-                const LiveHost h = !fairness ? live_host(m, prop, (u64)max_states)
-                                   : moves   ? live_host<true, true>(m, prop, (u64)max_states)
-                                             : live_host<true, false>(m, prop, (u64)max_states);
-                *out = h.r;
-                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.actions.size(); ++i) action_ids[i] = h.actions[i];
-                return (i64)h.unique;
-            } else {
-                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
-            }
-        });
-        if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host: model " + std::to_string(model) + " has no host form");
-        return r;
-    } catch (const Error& x) {
-        set_error(x.what());
-        return x.code;
-    } catch (const std::exception& x) {
-        set_error(x.what());
-        return SR_ERR_ARG;
-    }
+    const char* args = !out || max_states < 1            ? "sr_liveness_host: out and max_states >= 1"
+                       : fairness != 0 && fairness != 1 ? "sr_liveness_host_fair: fairness must be 0 (none) or 1 (progress)"
+                                                        : nullptr;
+    return liveness_host_entry("sr_liveness_host", args, nullptr, model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) {
+        return !fairness ? live_host(m, prop, (u64)max_states)
+               : moves   ? live_host<true, true>(m, prop, (u64)max_states)
+                         : live_host<true, false>(m, prop, (u64)max_states);
+    });
 }
 
 int32_t sr_gpu_bfs_liveness_weak(const sr_bfs* b, int32_t prop, sr_live_weak* out) {
@@ -724,44 +758,15 @@ int32_t sr_gpu_bfs_liveness_weak(const sr_bfs* b, int32_t prop, sr_live_weak* ou
 }
 
 int32_t sr_gpu_bfs_loop_fair(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t loop_start) {
-    if (!b || !b->e->finished.load(std::memory_order_acquire) || n < 0 || (n > 0 && !ids) || loop_start < 0 || loop_start > n) return -1;
-    try {
-        return b->e->loop_fair(init, ids, n, loop_start);
-    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
-        set_error(x.what());
-        return -1;
-    }
+    return loop_fair_entry(b, init, ids, n, loop_start, false);
 }
 
 int64_t sr_liveness_host_weak(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_live_result* out,
                               sr_live_weak* weak, int64_t* action_ids, int32_t cap) {
-    try {
-        if (!out || !weak || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host_weak: out, weak and max_states >= 1");
-        const char* e = std::getenv("SR_LIVE_MOVES");  // (as in sr_liveness_host_fair)
-        const bool moves = !e || std::atoi(e) != 0;
-        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
-            using M = std::decay_t<decltype(m)>;
-            if constexpr (has_emask<M>::value) {
-                const LiveHostWeak h = moves ? live_host_weak<true>(m, prop, (u64)max_states) : live_host_weak<false>(m, prop, (u64)max_states);
-                *out = h.h.r;
-                *weak = h.w;
-                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.h.actions.size(); ++i) action_ids[i] = h.h.actions[i];
-                return (i64)h.h.unique;
-            } else if constexpr (!fair_slots_model<M>) {
-                throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
-            } else {
-                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
-            }
-        });
-        if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host_weak: model " + std::to_string(model) + " has no host form");
-        return r;
-    } catch (const Error& x) {
-        set_error(x.what());
-        return x.code;
-    } catch (const std::exception& x) {
-        set_error(x.what());
-        return SR_ERR_ARG;
-    }
+    const char* args = !out || !weak || max_states < 1 ? "sr_liveness_host_weak: out, weak and max_states >= 1" : nullptr;
+    return liveness_host_entry("sr_liveness_host_weak", args, "weak fairness", model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) {
+        return live_host_split(moves ? live_host_weak<true>(m, prop, (u64)max_states) : live_host_weak<false>(m, prop, (u64)max_states), weak);
+    });
 }
 
 int32_t sr_gpu_bfs_liveness_strong(const sr_bfs* b, int32_t prop, sr_live_strong* out) {
@@ -770,44 +775,15 @@ int32_t sr_gpu_bfs_liveness_strong(const sr_bfs* b, int32_t prop, sr_live_strong
 }
 
 int32_t sr_gpu_bfs_loop_strongly_fair(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t loop_start) {
-    if (!b || !b->e->finished.load(std::memory_order_acquire) || n < 0 || (n > 0 && !ids) || loop_start < 0 || loop_start > n) return -1;
-    try {
-        return b->e->loop_fair(init, ids, n, loop_start, true);
-    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
-        set_error(x.what());
-        return -1;
-    }
+    return loop_fair_entry(b, init, ids, n, loop_start, true);
 }
 
 int64_t sr_liveness_host_strong(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_live_result* out,
                                 sr_live_strong* strong, int64_t* action_ids, int32_t cap) {
-    try {
-        if (!out || !strong || max_states < 1) throw Error(SR_ERR_ARG, "sr_liveness_host_strong: out, strong and max_states >= 1");
-        const char* e = std::getenv("SR_LIVE_MOVES");  // (as in sr_liveness_host_fair)
-        const bool moves = !e || std::atoi(e) != 0;
-        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
-            using M = std::decay_t<decltype(m)>;
-            if constexpr (has_emask<M>::value) {
-                const LiveHostStrong h = moves ? live_host_strong<true>(m, prop, (u64)max_states) : live_host_strong<false>(m, prop, (u64)max_states);
-                *out = h.h.r;
-                *strong = h.s;
-                for (int32_t i = 0; action_ids && i < cap && i < (int32_t)h.h.actions.size(); ++i) action_ids[i] = h.h.actions[i];
-                return (i64)h.h.unique;
-            } else if constexpr (!fair_slots_model<M>) {
-                throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
-            } else {
-                throw Error(SR_ERR_ARG, "liveness: the model has no `eventually` property");
-            }
-        });
-        if (r == SR_ERR_UNSUPPORTED) set_error("sr_liveness_host_strong: model " + std::to_string(model) + " has no host form");
-        return r;
-    } catch (const Error& x) {
-        set_error(x.what());
-        return x.code;
-    } catch (const std::exception& x) {
-        set_error(x.what());
-        return SR_ERR_ARG;
-    }
+    const char* args = !out || !strong || max_states < 1 ? "sr_liveness_host_strong: out, strong and max_states >= 1" : nullptr;
+    return liveness_host_entry("sr_liveness_host_strong", args, "strong fairness", model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) {
+        return live_host_split(moves ? live_host_strong<true>(m, prop, (u64)max_states) : live_host_strong<false>(m, prop, (u64)max_states), strong);
+    });
 }
 
 int64_t sr_host_graph(int32_t model, const int64_t* p, int32_t np, int64_t max_states, int64_t* out, int64_t cap) {

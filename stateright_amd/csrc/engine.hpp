@@ -90,7 +90,7 @@ class EngineBase {
     // The weak-fairness figures of that check (sr_gpu_bfs_liveness_weak); false: p is no property.
     virtual bool live_weak_result(int p, sr_live_weak* out) const {
         if (p < 0 || p >= nprops()) return false;
-        *out = p < (int)live_weak.size() ? live_weak[p] : live_weak_none();
+        *out = p < (int)live_weak.size() ? live_weak[p] : live_fair_none<sr_live_weak>();
         return true;
     }
     // Whether the loop of the lasso that the actions describe from init state `init` is weakly fair
@@ -102,7 +102,7 @@ class EngineBase {
     // The strong-fairness figures of that check (sr_gpu_bfs_liveness_strong); false: p is no property.
     bool live_strong_result(int p, sr_live_strong* out) const {
         if (p < 0 || p >= nprops()) return false;
-        *out = p < (int)live_strong.size() ? live_strong[p] : live_strong_none();
+        *out = p < (int)live_strong.size() ? live_strong[p] : live_fair_none<sr_live_strong>();
         return true;
     }
 
@@ -1439,12 +1439,12 @@ class Engine final : public EngineBase {
     // The arena is R, the final visited set names its states. Every buffer lives for this call only.
     // sr_opts.liveness = SR_LIVENESS_PROGRESS launches the FAIR instantiations of live_trim and
     // live_walk (progress fairness, live.hpp); SR_LIVENESS_WEAK launches the FAIR live_trim and then
-    // live_weak_pass below in place of the walk, SR_LIVENESS_STRONG likewise live_strong_pass; every other
-    // value launches the plain ones.
+    // live_weak_pass below in place of the walk, SR_LIVENESS_STRONG likewise live_strong_pass (both through
+    // live_fair_pass, over the stages of LiveFair); every other value launches the plain ones.
     void live_pass() {
         live.assign(M::NPROPS, live_result_none());
-        live_weak.assign(M::NPROPS, live_weak_none());
-        live_strong.assign(M::NPROPS, live_strong_none());
+        live_weak.assign(M::NPROPS, live_fair_none<sr_live_weak>());
+        live_strong.assign(M::NPROPS, live_fair_none<sr_live_strong>());
         if constexpr (has_emask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
             u32 todo = 0;
             for (int p = 0; p < M::NPROPS; ++p)
@@ -1521,15 +1521,9 @@ class Engine final : public EngineBase {
                                      r.rounds, h.removed, cnt, (unsigned long long)r.surviving);
                     if (!h.removed) break;
                 }
-                if (weak) {
-                    live_weak_pass(p, r, live_weak[p], n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
-                                   inits, k, walk_steps);
-                    r.pass_ms = secs(t0, Clock::now()) * 1e3;
-                    continue;
-                }
-                if (strong) {
-                    live_strong_pass(p, r, live_strong[p], n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
-                                     inits, k, walk_steps);
+                if (weak || strong) {
+                    live_fair_pass(strong, LivePassArgs{p, r, n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
+                                                        inits, k, walk_steps});
                     r.pass_ms = secs(t0, Clock::now()) * 1e3;
                     continue;
                 }
@@ -1577,17 +1571,7 @@ class Engine final : public EngineBase {
     // successor and whose successors all are the state itself.
     void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, u32 end, bool fair) {
         const size_t len = path.size() / W - 1;
-        const std::string name = m_.prop_name(p);
-        std::vector<i64> acts, described;
-        concrete_path(m_, path, acts, described);
-        for (size_t i = 0; i <= len; ++i)
-            if (!live_not_p(m_, p, &path[i * W]))
-                throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
-        if (fair)
-            for (size_t i = 0; i < len; ++i)
-                if (std::equal(&path[i * W], &path[i * W] + W, &path[(i + 1) * W]))
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: step " + std::to_string(i) + " of the witness of \"" + name +
-                                                           "\" returns its own state (progress fairness steps over no self-loop)");
+        const std::string name = live_replay(p, path, fair);
         const u64* last = &path[len * W];
         if (end == LIVE_WALK_LOOP) {
             size_t j = 0;
@@ -1610,493 +1594,421 @@ class Engine final : public EngineBase {
                 r.end_kind = SR_LIVE_END_TERMINAL;
             }
         }
-        r.witness_len = (int64_t)len;
+        live_found(p, r, path);
+    }
+
+    // A fair mode's lasso, replayed on the host model before it becomes the discovery of p: live_replay's checks
+    // with fair = true, the last state equals the state at loop_start word for word, and the loop is weakly fair
+    // on its own states and steps (live.hpp live_loop_fair); strong: strongly fair (live_loop_strong_fair). A
+    // path that fails is an engine error, never a discovery.
+    void live_accept_loop(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start, bool strong) {
+        const size_t len = path.size() / W - 1;
+        const std::string name = live_replay(p, path, true);
+        if (loop_start >= len || !std::equal(&path[len * W], &path[len * W] + W, &path[loop_start * W]))
+            throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" does not end where it starts");
+        if (strong ? !live_loop_strong_fair(m_, &path[loop_start * W], len - loop_start)
+                   : !live_loop_fair(m_, &path[loop_start * W], len - loop_start))
+            throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" is not " +
+                                                   (strong ? "strongly" : "weakly") + " fair");
+        r.loop_start = (int64_t)loop_start;
+        r.end_kind = SR_LIVE_END_LOOP;
+        live_found(p, r, path);
+    }
+
+    // What every acceptance checks first: every step is a successor in `actions()` order (concrete_path), the
+    // condition of p holds on no state, and (fair) no step returns its own state. The property's name.
+    std::string live_replay(int p, const std::vector<u64>& path, bool fair) {
+        const size_t len = path.size() / W - 1;
+        const std::string name = m_.prop_name(p);
+        std::vector<i64> acts, described;
+        concrete_path(m_, path, acts, described);
+        for (size_t i = 0; i <= len; ++i)
+            if (!live_not_p(m_, p, &path[i * W]))
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
+        if (fair)
+            for (size_t i = 0; i < len; ++i)
+                if (std::equal(&path[i * W], &path[i * W] + W, &path[(i + 1) * W]))
+                    throw Error(SR_ERR_NONDETERMINISM, "liveness: step " + std::to_string(i) + " of the witness of \"" + name +
+                                                           "\" returns its own state (a fair mode steps over no self-loop)");
+        return name;
+    }
+    // An accepted witness becomes the discovery of p.
+    void live_found(int p, sr_live_result& r, const std::vector<u64>& path) {
+        r.witness_len = (int64_t)(path.size() / W - 1);
         live_path_[p] = path;
         disc[p].found = true;
         disc[p].level = disc[p].rank = 0;
     }
-    // WEAK FAIRNESS (live.hpp; the kernels' header in kernels_live.hpp), behind live_mark and the progress
-    // trim of property p: np the list live_mark wrote, u0 the trim's last worklist (F_p' minus its sinks), spare
-    // the other worklist buffer. One counter read-back per round, as in the trim. Every buffer lives for this
-    // call only: 4 bytes per table slot (slot -> arena index), 8 bytes per arena state (rank, component), three
-    // worklists of 4 bytes per state of N_p; only if F_p' has a cycle 12 bytes more per arena state (colour, stamp,
-    // component size) and 16 MW bytes of accumulators; only for a lasso 4 bytes more (ranks inside the component).
-    void live_weak_pass(int p, sr_live_result& r, sr_live_weak& wk, u32 n, const TableView& t, size_t bwords, const u64* slot_of,
-                        const u32* alive, const u32* np, u32 np_cnt, u32* u0, u32 u0_cnt, u32* spare, const std::vector<u64>& inits,
-                        u32 k, u32 walk_steps) {
-        if constexpr (fair_slots_model<M> && M::MW <= LIVE_MW_MAX) {
-            constexpr int MW = M::MW;
-            const auto t0 = Clock::now();
-            const int dev = o_.device;
-            wk.ran = 1;
-            DBuf<u32> ubits, idx, rank, lrank, colour, stamp, comp, size, third;
-            DBuf<u64> and_me, or_took, wcb, lcb, out;
-            ubits.alloc(dev, bwords);
-            idx.alloc(dev, (size_t)cap_);
-            rank.alloc(dev, n);
-            comp.alloc(dev, n);
-            third.alloc(dev, np_cnt);
+
+    // What live_pass hands a fair pass, behind live_mark and the progress trim of property p: np the list
+    // live_mark wrote, u0 the trim's last worklist (F_p' minus its sinks), spare the other worklist buffer.
+    struct LivePassArgs {
+        int p;
+        sr_live_result& r;
+        u32 n;
+        const TableView& t;
+        size_t bwords;
+        const u64* slot_of;
+        const u32* alive;
+        const u32* np;
+        u32 np_cnt;
+        u32* u0;
+        u32 u0_cnt;
+        u32* spare;
+        const std::vector<u64>& inits;
+        u32 k, walk_steps;
+    };
+
+    // WEAK and STRONG FAIRNESS (live.hpp; the kernels' headers in kernels_live.hpp): what the two passes share,
+    // each stage written once. `bits` is the bitmap of the set the component search runs on (the weak mode's U,
+    // the strong mode's W), L its list, X and Y the two other list buffers, cnt its size. One counter read-back
+    // per round, as in the progress trim. Every buffer lives for the pass only: 4 bytes per table slot (slot ->
+    // arena index), 8 bytes per arena state (rank, component), three worklists of 4 bytes per state of N_p; only
+    // if F_p' has a cycle (alloc_search) 12 bytes more per arena state (colour, stamp, component size) and
+    // 16 MW bytes of accumulators; only for a lasso 4 bytes more (ranks inside the component).
+    template <class Stats>  // sr_live_weak or sr_live_strong
+    struct LiveFair {
+        static constexpr int MW = M::MW;
+        static constexpr size_t HEAD = offsetof(LiveWeakCounters, notme);  // (the masks behind it live across launches)
+        Engine& e;
+        const LivePassArgs& a;
+        Stats& s;
+        const Clock::time_point t0 = Clock::now();
+        DBuf<u32> bits, idx, rank, lrank, colour, stamp, comp, size, third;
+        DBuf<u64> acc_me, or_took, wcb, lcb, out;  // acc_me: the weak mode's and_me, the strong mode's or_me
+        LiveWeakCounters* wc = nullptr;
+        LiveCounters* lc = nullptr;
+        LiveWeakCounters hw{};
+        u32 *L = nullptr, *X = nullptr, *Y = nullptr;
+        u32 cnt = 0, round = 0;
+        std::vector<u64> path;  // the witness' states
+        u64 bound = 0;          // and how many steps it may have
+        u32 g = 0, root = ~0u;  // the stem's last state and its component (by arena index)
+        u64 c_mask[MW];         // acc_me of that component
+
+        LiveFair(Engine& e_, const LivePassArgs& a_, Stats& s_) : e(e_), a(a_), s(s_) {}
+
+        void fail(u32 err) const {
+            if (err & LIVE_ERR_LOOKUP)
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: find_slot did not find a reachable state, or a successor of one, in the "
+                                                   "visited set (an engine error: such a state is never taken as \"not alive\")");
+            if (err & LIVE_ERR_STUCK)
+                throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state of the witness has no successor of a lower rank, or a "
+                                                   "member of a level has no component");
+        }
+        void clear_head() { SR_HIP(hipMemsetAsync(wc, 0, HEAD, e.stream_)); }
+        void read_w() {  // the launch's counters (waits for it)
+            SR_HIP(hipGetLastError());
+            SR_HIP(hipMemcpyAsync(&hw, wc, sizeof(hw), hipMemcpyDeviceToHost, e.stream_));
+            SR_HIP(stream_sync(e.stream_));
+            fail(hw.err);
+        }
+
+        // The buffers every run needs; the bitmap from u0, the slot -> arena index map and rank 0 for the sinks.
+        void setup() {
+            const int dev = e.o_.device;
+            s.ran = 1;
+            bits.alloc(dev, a.bwords);
+            idx.alloc(dev, (size_t)e.cap_);
+            rank.alloc(dev, a.n);
+            comp.alloc(dev, a.n);
+            third.alloc(dev, a.np_cnt);
             wcb.alloc(dev, (sizeof(LiveWeakCounters) + 7) / 8);
             lcb.alloc(dev, (sizeof(LiveCounters) + 7) / 8);
-            LiveWeakCounters* wc = reinterpret_cast<LiveWeakCounters*>(wcb.p);
-            LiveCounters* lc = reinterpret_cast<LiveCounters*>(lcb.p);
-            LiveWeakCounters hw{};
-            constexpr size_t HEAD = offsetof(LiveWeakCounters, notme);  // (the masks behind it live across launches)
-            auto fail = [&](u32 err) {
-                if (err & LIVE_ERR_LOOKUP)
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: find_slot did not find a reachable state, or a successor of one, in the "
-                                                       "visited set (an engine error: such a state is never taken as \"not alive\")");
-                if (err & LIVE_ERR_STUCK)
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state of the witness has no successor of a lower rank");
-            };
-            auto clear_head = [&] { SR_HIP(hipMemsetAsync(wc, 0, HEAD, stream_)); };
-            auto read_w = [&] {  // the launch's counters (waits for it)
-                SR_HIP(hipGetLastError());
-                SR_HIP(hipMemcpyAsync(&hw, wc, sizeof(hw), hipMemcpyDeviceToHost, stream_));
-                SR_HIP(stream_sync(stream_));
-                fail(hw.err);
-            };
-            SR_HIP(hipMemsetAsync(ubits.p, 0, bwords * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(idx.p, 0xff, (size_t)cap_ * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(rank.p, 0xff, (size_t)n * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(comp.p, 0xff, (size_t)n * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), stream_));
-            if (u0_cnt) live_set_bits<><<<blocks_for(u0_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(u0, u0_cnt, slot_of, ubits.p);
-            if (np_cnt) live_index<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, ubits.p, idx.p, rank.p);
-            // U: trimmed to the states with a successor in U (the progress trim's kernel on the U bitmap)
-            u32 *L = u0, *X = spare, *Y = third.p;
-            u32 cnt = u0_cnt;
+            wc = reinterpret_cast<LiveWeakCounters*>(wcb.p);
+            lc = reinterpret_cast<LiveCounters*>(lcb.p);
+            SR_HIP(hipMemsetAsync(bits.p, 0, a.bwords * sizeof(u32), e.stream_));
+            SR_HIP(hipMemsetAsync(idx.p, 0xff, (size_t)e.cap_ * sizeof(u32), e.stream_));
+            SR_HIP(hipMemsetAsync(rank.p, 0xff, (size_t)a.n * sizeof(u32), e.stream_));
+            SR_HIP(hipMemsetAsync(comp.p, 0xff, (size_t)a.n * sizeof(u32), e.stream_));
+            SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), e.stream_));
+            if (a.u0_cnt)
+                live_set_bits<><<<blocks_for(a.u0_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(a.u0, a.u0_cnt, a.slot_of, bits.p);
+            if (a.np_cnt)
+                live_index<><<<blocks_for(a.np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(a.np, a.np_cnt, a.slot_of, a.alive, bits.p,
+                                                                                             idx.p, rank.p);
+            L = a.u0, X = a.spare, Y = third.p;
+            cnt = a.u0_cnt;
+        }
+
+        // The set trimmed to the states with a successor in it (the progress trim's kernel on `bits`).
+        void trim() {
             while (cnt) {
                 LiveCounters h{};
-                SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
-                live_trim<M, true><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of, ubits.p, L, cnt, X, lc);
+                SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), e.stream_));
+                live_trim<M, true><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(e.m_, e.arena_.p, a.t, a.slot_of, bits.p, L, cnt, X,
+                                                                                              lc);
                 SR_HIP(hipGetLastError());
-                SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, stream_));
-                SR_HIP(stream_sync(stream_));
+                SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, e.stream_));
+                SR_HIP(stream_sync(e.stream_));
                 fail(h.err & LIVE_ERR_LOOKUP);
+                if (h.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a trim round lists more states than its set has");
                 std::swap(L, X);
                 cnt = h.next_n;
-                wk.scc_rounds += 1;
+                s.scc_rounds += 1;
                 if (!h.removed) break;
             }
-            wk.cyclic_states = cnt;
-            const bool cyclic = cnt != 0;  // (U is not empty iff F_p' has a cycle, iff there is a component)
-            if (cyclic) {  // what only the component search and the components' fairness need
-                colour.alloc(dev, n);
-                stamp.alloc(dev, n);
-                size.alloc(dev, n);
-                and_me.alloc(dev, (size_t)n * MW);
-                or_took.alloc(dev, (size_t)n * MW);
-                SR_HIP(hipMemsetAsync(stamp.p, 0, (size_t)n * sizeof(u32), stream_));
-                SR_HIP(hipMemsetAsync(size.p, 0, (size_t)n * sizeof(u32), stream_));
-                SR_HIP(hipMemsetAsync(and_me.p, 0xff, (size_t)n * MW * sizeof(u64), stream_));
-                SR_HIP(hipMemsetAsync(or_took.p, 0, (size_t)n * MW * sizeof(u64), stream_));
-            }
-            // the components of U: colour, find the roots' components, take them out, until U is empty
-            u32 round = 0;
+        }
+
+        // What only the component search and the components' accumulators need. The mode initialises size, acc_me
+        // and or_took: the weak mode once (and_me starts as all ones), the strong mode per level (live_level_open).
+        void alloc_search() {
+            const int dev = e.o_.device;
+            colour.alloc(dev, a.n);
+            stamp.alloc(dev, a.n);
+            size.alloc(dev, a.n);
+            acc_me.alloc(dev, (size_t)a.n * MW);
+            or_took.alloc(dev, (size_t)a.n * MW);
+            SR_HIP(hipMemsetAsync(stamp.p, 0, (size_t)a.n * sizeof(u32), e.stream_));
+        }
+
+        // The components of the set: colour, find the roots' components, take them out, until it is empty.
+        void components() {
             while (cnt) {
-                live_colour_init<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p);
+                live_colour_init<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(L, cnt, colour.p);
                 u32 *src = L, *dst = X, sn = cnt;
                 while (sn) {
                     clear_head();
-                    live_colour_push<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, ubits.p, colour.p, stamp.p,
-                                                                                               ++round, src, sn, dst, wc);
+                    live_colour_push<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(e.m_, e.arena_.p, a.t, idx.p, bits.p, colour.p,
+                                                                                                  stamp.p, ++round, src, sn, dst, wc);
                     read_w();
-                    wk.scc_rounds += 1;
-                    if (hw.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a colouring round lists more states than U has");
+                    s.scc_rounds += 1;
+                    if (hw.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a colouring round lists more states than its set has");
                     sn = hw.next_n;
                     src = dst;
                     dst = src == X ? Y : X;
                 }
-                live_scc_seed<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p, comp.p);
+                live_scc_seed<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(L, cnt, colour.p, comp.p);
                 src = L, dst = X, sn = cnt;
                 for (;;) {
                     clear_head();
-                    live_scc_join<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, ubits.p, colour.p, comp.p, src, sn,
-                                                                                            dst, wc);
+                    live_scc_join<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(e.m_, e.arena_.p, a.t, idx.p, bits.p, colour.p, comp.p,
+                                                                                               src, sn, dst, wc);
                     read_w();
-                    wk.scc_rounds += 1;
+                    s.scc_rounds += 1;
+                    if (hw.next_n > sn) throw Error(SR_ERR_HIP, "liveness: a join round lists more states than it was given");
                     sn = hw.next_n;
                     src = dst;
                     dst = src == X ? Y : X;
                     if (!hw.joined || !sn) break;
                 }
-                if (sn >= cnt) throw Error(SR_ERR_HIP, "liveness: a round of the component search took no state out of U");
-                live_scc_leave<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, slot_of, comp.p, ubits.p);
-                std::swap(L, src == X ? X : Y);  // (what has not joined is the next U)
+                if (sn >= cnt) throw Error(SR_ERR_HIP, "liveness: a round of the component search took no state out of its set");
+                live_scc_leave<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(L, cnt, a.slot_of, comp.p, bits.p);
+                std::swap(L, src == X ? X : Y);  // (what has not joined is the next set)
                 cnt = sn;
             }
-            // fairness per component, the goal set, ranks towards it over F_p'
-            clear_head();
-            u32 sn = 0;
-            if (np_cnt) {
-                if (cyclic)  // (without a component live_goal reads none of size, and_me, or_took: comp is ~0 everywhere)
-                    live_comp_acc<M><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, np, np_cnt, size.p,
-                                                                                                and_me.p, or_took.p, wc);
-                live_goal<M><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, comp.p, size.p, and_me.p,
-                                                                                        or_took.p, rank.p, L, wc);
-                read_w();
-                wk.components = hw.comps;
-                wk.fair_components = hw.fair_comps;
-                wk.goal_states = wk.fair_states = hw.goal;
-                sn = hw.next_n;
-            }
-            auto reach = [&](u32* rk, u32* src, u32* dst, u32 todo) {  // levels until one ranks nothing
-                for (u32 level = 1; todo; ++level) {
-                    clear_head();
-                    live_reach<M><<<blocks_for(todo, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, rk, level, src, todo, dst, wc);
-                    read_w();
-                    wk.reach_rounds += 1;
-                    if (rk == rank.p) wk.fair_states += hw.joined;
-                    if (!hw.joined) break;
-                    todo = hw.next_n;
-                    std::swap(src, dst);
-                }
-            };
-            if (wk.goal_states) reach(rank.p, L, X, sn);
-            clear_head();
-            SR_HIP(hipMemsetAsync(&wc->first_init, 0xff, sizeof(u32), stream_));
-            live_first_ranked<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of, idx.p, rank.p, k, wc);
-            read_w();
-            if (hw.first_init < k) r.init_index = (int32_t)hw.first_init;
-            if (r.init_index >= 0) {
-                out.alloc(dev, ((size_t)walk_steps + 2) * W);
-                std::vector<u64> path(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
-                SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
-                const u64 bound = ((u64)A_ + 2) * (r.surviving + 1);  // the stem and A + 1 segments, each a simple path
-                auto descend = [&](const u32* rk, int then, u32 all) {  // (each launch but the last takes walk_steps steps)
-                    for (;;) {
-                        clear_head();
-                        live_descend<M><<<1, 64, 0, stream_>>>(m_, t, idx.p, rk, out.p, walk_steps, then, all, wc);
-                        read_w();
-                        if (hw.steps > walk_steps + 1) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
-                        const size_t o = path.size();
-                        path.resize(o + (size_t)hw.steps * W);
-                        if (hw.steps) {
-                            SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)hw.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
-                            SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)hw.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
-                        }
-                        if (path.size() / W - 1 > bound) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than its bound");
-                        if (hw.end == LIVE_DESCEND_DONE) break;
-                        if (!hw.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
-                    }
-                };
-                descend(rank.p, -1, 0);
-                wk.stem_len = (int64_t)(path.size() / W - 1);
-                const u32 g = hw.last_idx;
-                if (g >= n) throw Error(SR_ERR_HIP, "liveness: the stem's last state has no arena index");
-                u32 root = ~0u;
-                SR_HIP(hipMemcpy(&root, comp.p + g, sizeof(u32), hipMemcpyDeviceToHost));
-                if (root == ~0u) {  // a sink of F_p': terminal, or a stutter end (live_accept checks which)
-                    u64 all = 0;
-                    for_each_successor(m_, &path[path.size() - W], [&](int, const u64*) { ++all; });
-                    wk.loop_len = 0;
-                    live_accept(p, r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true);
-                } else {
-                    if (root >= n) throw Error(SR_ERR_HIP, "liveness: the stem ends in a component without a root");
-                    u64 c_and[MW];
-                    SR_HIP(hipMemcpy(c_and, and_me.p + (size_t)root * MW, sizeof(c_and), hipMemcpyDeviceToHost));
-                    lrank.alloc(dev, n);
-                    SR_HIP(hipMemsetAsync(lrank.p, 0xff, (size_t)n * sizeof(u32), stream_));
-                    clear_head();
-                    live_members<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, comp.p, root, Y, wc);
-                    read_w();
-                    const u32 mcnt = hw.next_n;
-                    auto segment = [&](int plan, int a) {
-                        clear_head();
-                        live_targets<M><<<blocks_for(mcnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, root, plan, a, g, Y, mcnt,
-                                                                                                 lrank.p, L, wc);
-                        read_w();
-                        if (!hw.joined) throw Error(SR_ERR_NONDETERMINISM, "liveness: a segment of the closed walk has no target in its component");
-                        reach(lrank.p, L, X, hw.next_n);
-                        wk.segments += 1;
-                        descend(lrank.p, plan == LIVE_PLAN_TAKE ? a : -1, 1);
-                    };
-                    for (int a = 0; a < (int)A_; ++a) {
-                        const int plan = live_loop_plan(a, hw.notme, hw.taken, c_and);
-                        if (plan != LIVE_PLAN_SKIP) segment(plan, a);
-                    }
-                    segment(LIVE_PLAN_HOME, 0);
-                    wk.loop_len = (int64_t)(path.size() / W - 1) - wk.stem_len;
-                    live_accept_weak(p, r, path, (size_t)wk.stem_len);
-                }
-            }
-            wk.pass_ms = secs(t0, Clock::now()) * 1e3;
-        } else {
-            (void)p, (void)r, (void)wk, (void)n, (void)t, (void)bwords, (void)slot_of, (void)alive, (void)np, (void)np_cnt, (void)u0, (void)u0_cnt,
-                (void)spare, (void)inits, (void)k, (void)walk_steps;
-            throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
         }
-    }
 
-    // STRONG FAIRNESS (live.hpp; the kernels' header in kernels_live.hpp), behind live_mark and the progress
-    // trim of property p, with the weak pass' arguments. The host form's recursive tree becomes level-synchronous
-    // rounds over all open components at once: W starts as the weak mode's U; a level takes the components of
-    // G'[W] (the weak mode's colour, seed, join and leave kernels over the W bitmap), accumulates or_me and
-    // or_took per component (live_comp_acc_or), lets live_refine freeze the fair nodes, drop the states that
-    // enable a bad slot and hand the rest back to W, and trims W again; until W is empty. One counter read-back
-    // per round. Memory is the weak pass' plus one list of 4 bytes per state of N_p (the level's members); no
-    // level stamp is kept per state, because live_refine clears the component number of every state that is
-    // not frozen.
-    void live_strong_pass(int p, sr_live_result& r, sr_live_strong& sg, u32 n, const TableView& t, size_t bwords, const u64* slot_of,
-                          const u32* alive, const u32* np, u32 np_cnt, u32* u0, u32 u0_cnt, u32* spare, const std::vector<u64>& inits,
-                          u32 k, u32 walk_steps) {
-        if constexpr (fair_slots_model<M> && M::MW <= LIVE_MW_MAX) {
-            constexpr int MW = M::MW;
-            const auto t0 = Clock::now();
-            const int dev = o_.device;
-            sg.ran = 1;
-            DBuf<u32> wbits, idx, rank, lrank, colour, stamp, comp, size, third, lvl;
-            DBuf<u64> or_me, or_took, wcb, lcb, out;
-            wbits.alloc(dev, bwords);
-            idx.alloc(dev, (size_t)cap_);
-            rank.alloc(dev, n);
-            comp.alloc(dev, n);
-            third.alloc(dev, np_cnt);
-            wcb.alloc(dev, (sizeof(LiveWeakCounters) + 7) / 8);
-            lcb.alloc(dev, (sizeof(LiveCounters) + 7) / 8);
-            LiveWeakCounters* wc = reinterpret_cast<LiveWeakCounters*>(wcb.p);
-            LiveCounters* lc = reinterpret_cast<LiveCounters*>(lcb.p);
-            LiveWeakCounters hw{};
-            constexpr size_t HEAD = offsetof(LiveWeakCounters, notme);  // (the masks behind it live across launches)
-            auto fail = [&](u32 err) {
-                if (err & LIVE_ERR_LOOKUP)
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: find_slot did not find a reachable state, or a successor of one, in the "
-                                                       "visited set (an engine error: such a state is never taken as \"not alive\")");
-                if (err & LIVE_ERR_STUCK)
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state of the witness has no successor of a lower rank, or a "
-                                                       "member of a level has no component");
-            };
-            auto clear_head = [&] { SR_HIP(hipMemsetAsync(wc, 0, HEAD, stream_)); };
-            auto read_w = [&] {  // the launch's counters (waits for it)
-                SR_HIP(hipGetLastError());
-                SR_HIP(hipMemcpyAsync(&hw, wc, sizeof(hw), hipMemcpyDeviceToHost, stream_));
-                SR_HIP(stream_sync(stream_));
-                fail(hw.err);
-            };
-            SR_HIP(hipMemsetAsync(wbits.p, 0, bwords * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(idx.p, 0xff, (size_t)cap_ * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(rank.p, 0xff, (size_t)n * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(comp.p, 0xff, (size_t)n * sizeof(u32), stream_));
-            SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), stream_));
-            if (u0_cnt) live_set_bits<><<<blocks_for(u0_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(u0, u0_cnt, slot_of, wbits.p);
-            if (np_cnt) live_index<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, wbits.p, idx.p, rank.p);
-            u32 *L = u0, *X = spare, *Y = third.p;
-            u32 cnt = u0_cnt;
-            // W: trimmed to the states with a successor in W (the progress trim's kernel on the W bitmap)
-            auto trim_w = [&] {
-                while (cnt) {
-                    LiveCounters h{};
-                    SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
-                    live_trim<M, true><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, slot_of, wbits.p, L, cnt, X, lc);
-                    SR_HIP(hipGetLastError());
-                    SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, stream_));
-                    SR_HIP(stream_sync(stream_));
-                    fail(h.err & LIVE_ERR_LOOKUP);
-                    if (h.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a trim round lists more states than W has");
-                    std::swap(L, X);
-                    cnt = h.next_n;
-                    sg.scc_rounds += 1;
-                    if (!h.removed) break;
-                }
-            };
-            trim_w();
-            sg.cyclic_states = cnt;
-            if (cnt) {  // what only the component search and the components' fairness need
-                colour.alloc(dev, n);
-                stamp.alloc(dev, n);
-                size.alloc(dev, n);
-                or_me.alloc(dev, (size_t)n * MW);
-                or_took.alloc(dev, (size_t)n * MW);
-                lvl.alloc(dev, cnt);
-                SR_HIP(hipMemsetAsync(stamp.p, 0, (size_t)n * sizeof(u32), stream_));
-            }
-            u32 round = 0;
-            u64 frozen = 0;
-            while (cnt) {  // one level of the tree
-                const u32 members = cnt;
-                SR_HIP(hipMemcpyAsync(lvl.p, L, (size_t)members * sizeof(u32), hipMemcpyDeviceToDevice, stream_));
-                live_level_open<MW><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(lvl.p, members, size.p, or_me.p, or_took.p);
-                // the components of W: colour, find the roots' components, take them out, until W is empty
-                while (cnt) {
-                    live_colour_init<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p);
-                    u32 *src = L, *dst = X, sn = cnt;
-                    while (sn) {
-                        clear_head();
-                        live_colour_push<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, wbits.p, colour.p, stamp.p,
-                                                                                                   ++round, src, sn, dst, wc);
-                        read_w();
-                        sg.scc_rounds += 1;
-                        if (hw.next_n > cnt) throw Error(SR_ERR_HIP, "liveness: a colouring round lists more states than W has");
-                        sn = hw.next_n;
-                        src = dst;
-                        dst = src == X ? Y : X;
-                    }
-                    live_scc_seed<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, colour.p, comp.p);
-                    src = L, dst = X, sn = cnt;
-                    for (;;) {
-                        clear_head();
-                        live_scc_join<M><<<blocks_for(sn, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, wbits.p, colour.p, comp.p, src,
-                                                                                                sn, dst, wc);
-                        read_w();
-                        sg.scc_rounds += 1;
-                        if (hw.next_n > sn) throw Error(SR_ERR_HIP, "liveness: a join round lists more states than it was given");
-                        sn = hw.next_n;
-                        src = dst;
-                        dst = src == X ? Y : X;
-                        if (!hw.joined || !sn) break;
-                    }
-                    if (sn >= cnt) throw Error(SR_ERR_HIP, "liveness: a round of the component search took no state out of W");
-                    live_scc_leave<><<<blocks_for(cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(L, cnt, slot_of, comp.p, wbits.p);
-                    std::swap(L, src == X ? X : Y);  // (what has not joined is the next W of this search)
-                    cnt = sn;
-                }
-                // the level's components: accumulate, then freeze, drop or hand back every member
+        // Ranks towards rank 0 in rk over the `todo` states listed in src: levels until one ranks nothing.
+        void reach(u32* rk, u32* src, u32* dst, u32 todo) {
+            for (u32 level = 1; todo; ++level) {
                 clear_head();
-                live_comp_acc_or<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, lvl.p, members, size.p,
-                                                                                                or_me.p, or_took.p, wc);
-                live_refine<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, slot_of, lvl.p, members, comp.p, size.p,
-                                                                                           or_me.p, or_took.p, wbits.p, L, wc);
+                live_reach<M><<<blocks_for(todo, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(e.m_, e.arena_.p, a.t, idx.p, rk, level, src, todo, dst,
+                                                                                          wc);
                 read_w();
-                if (hw.next_n >= members) throw Error(SR_ERR_HIP, "liveness: a level of the decomposition removed no state from W");
-                if (hw.comps) sg.levels += 1;
-                sg.components += hw.comps;
-                sg.fair_components += hw.fair_comps;
-                frozen += hw.joined;
-                cnt = hw.next_n;
-                if (o_.verbose)
-                    std::fprintf(stderr, "[sr] liveness \"%s\" level %u: %u members, %u components (%u fair), %u back in W\n", m_.prop_name(p),
-                                 sg.levels, members, hw.comps, hw.fair_comps, cnt);
-                trim_w();
+                s.reach_rounds += 1;
+                if (rk == rank.p) s.fair_states += hw.joined;
+                if (!hw.joined) break;
+                todo = hw.next_n;
+                std::swap(src, dst);
             }
-            // the goal set, ranks towards it over F_p'
+        }
+
+        // The init state of lowest index with a rank, into r.init_index; whether there is one.
+        bool first_ranked() {
             clear_head();
-            u32 sn = 0;
-            if (np_cnt) {
-                live_goal_strong<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, slot_of, alive, comp.p, rank.p, L, wc);
-                read_w();
-                sg.goal_states = sg.fair_states = hw.goal;
-                sn = hw.next_n;
-                if (hw.goal < frozen) throw Error(SR_ERR_HIP, "liveness: the goal set lost a frozen state");
-            }
-            auto reach = [&](u32* rk, u32* src, u32* dst, u32 todo) {  // levels until one ranks nothing
-                for (u32 level = 1; todo; ++level) {
-                    clear_head();
-                    live_reach<M><<<blocks_for(todo, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, rk, level, src, todo, dst, wc);
-                    read_w();
-                    sg.reach_rounds += 1;
-                    if (rk == rank.p) sg.fair_states += hw.joined;
-                    if (!hw.joined) break;
-                    todo = hw.next_n;
-                    std::swap(src, dst);
-                }
-            };
-            if (sg.goal_states) reach(rank.p, L, X, sn);
-            clear_head();
-            SR_HIP(hipMemsetAsync(&wc->first_init, 0xff, sizeof(u32), stream_));
-            live_first_ranked<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of, idx.p, rank.p, k, wc);
+            SR_HIP(hipMemsetAsync(&wc->first_init, 0xff, sizeof(u32), e.stream_));
+            live_first_ranked<><<<1, LIVE_BLOCK, 0, e.stream_>>>(a.slot_of, idx.p, rank.p, a.k, wc);
             read_w();
-            if (hw.first_init < k) r.init_index = (int32_t)hw.first_init;
-            if (r.init_index >= 0) {
-                out.alloc(dev, ((size_t)walk_steps + 2) * W);
-                std::vector<u64> path(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
-                SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
-                const u64 bound = ((u64)A_ + 2) * (r.surviving + 1);  // the stem and A + 1 segments, each a simple path
-                auto descend = [&](const u32* rk, int then, u32 all) {  // (each launch but the last takes walk_steps steps)
-                    for (;;) {
-                        clear_head();
-                        live_descend<M><<<1, 64, 0, stream_>>>(m_, t, idx.p, rk, out.p, walk_steps, then, all, wc);
-                        read_w();
-                        if (hw.steps > walk_steps + 1) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
-                        const size_t o = path.size();
-                        path.resize(o + (size_t)hw.steps * W);
-                        if (hw.steps) {
-                            SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)hw.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
-                            SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)hw.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
-                        }
-                        if (path.size() / W - 1 > bound) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than its bound");
-                        if (hw.end == LIVE_DESCEND_DONE) break;
-                        if (!hw.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
-                    }
-                };
-                descend(rank.p, -1, 0);
-                sg.stem_len = (int64_t)(path.size() / W - 1);
-                const u32 g = hw.last_idx;
-                if (g >= n) throw Error(SR_ERR_HIP, "liveness: the stem's last state has no arena index");
-                u32 root = ~0u;
-                SR_HIP(hipMemcpy(&root, comp.p + g, sizeof(u32), hipMemcpyDeviceToHost));
-                if (root == ~0u) {  // a sink of F_p': terminal, or a stutter end (live_accept checks which)
-                    u64 all = 0;
-                    for_each_successor(m_, &path[path.size() - W], [&](int, const u64*) { ++all; });
-                    sg.loop_len = 0;
-                    live_accept(p, r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true);
-                } else {
-                    if (root >= n) throw Error(SR_ERR_HIP, "liveness: the stem ends in a fair node without a root");
-                    u64 c_or[MW];
-                    SR_HIP(hipMemcpy(c_or, or_me.p + (size_t)root * MW, sizeof(c_or), hipMemcpyDeviceToHost));
-                    lrank.alloc(dev, n);
-                    SR_HIP(hipMemsetAsync(lrank.p, 0xff, (size_t)n * sizeof(u32), stream_));
-                    SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), stream_));  // (the stem's masks are not the loop's)
-                    live_members<><<<blocks_for(np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(np, np_cnt, comp.p, root, Y, wc);
-                    read_w();
-                    const u32 mcnt = hw.next_n;
-                    auto segment = [&](int plan, int a) {
-                        clear_head();
-                        live_targets<M><<<blocks_for(mcnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, t, idx.p, comp.p, root, plan, a, g, Y, mcnt,
-                                                                                                 lrank.p, L, wc);
-                        read_w();
-                        if (!hw.joined) throw Error(SR_ERR_NONDETERMINISM, "liveness: a segment of the closed walk has no target in its fair node");
-                        reach(lrank.p, L, X, hw.next_n);
-                        sg.segments += 1;
-                        descend(lrank.p, plan == LIVE_PLAN_TAKE ? a : -1, 1);
-                    };
-                    for (int a = 0; a < (int)A_; ++a)
-                        if (live_strong_plan(a, hw.taken, c_or) == LIVE_PLAN_TAKE) segment(LIVE_PLAN_TAKE, a);
-                    segment(LIVE_PLAN_HOME, 0);
-                    sg.loop_len = (int64_t)(path.size() / W - 1) - sg.stem_len;
-                    live_accept_weak(p, r, path, (size_t)sg.stem_len, true);
+            if (hw.first_init < a.k) a.r.init_index = (int32_t)hw.first_init;
+            return a.r.init_index >= 0;
+        }
+
+        // From the path's last state down the ranks rk to rank 0, then slot `then` (each launch but the last
+        // takes walk_steps steps).
+        void descend(const u32* rk, int then, u32 all) {
+            const u32 walk_steps = a.walk_steps;
+            for (;;) {
+                clear_head();
+                live_descend<M><<<1, 64, 0, e.stream_>>>(e.m_, a.t, idx.p, rk, out.p, walk_steps, then, all, wc);
+                read_w();
+                if (hw.steps > walk_steps + 1) throw Error(SR_ERR_HIP, "liveness: a witness launch reports more steps than its bound");
+                const size_t o = path.size();
+                path.resize(o + (size_t)hw.steps * W);
+                if (hw.steps) {
+                    SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)hw.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
+                    SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)hw.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, e.stream_));
                 }
+                if (path.size() / W - 1 > bound) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than its bound");
+                if (hw.end == LIVE_DESCEND_DONE) break;
+                if (!hw.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
             }
-            sg.pass_ms = secs(t0, Clock::now()) * 1e3;
+        }
+
+        // The stem from the init state first_ranked() found to rank 0 at g. A sink of F_p' ends the witness there
+        // (terminal, or a stutter end: live_accept checks which) and stem() returns false; otherwise g lies in
+        // the component `root`, whose acc_me mask is read into c_mask, and a closed walk has to follow.
+        bool stem() {
+            const std::vector<u64>& inits = a.inits;
+            out.alloc(e.o_.device, ((size_t)a.walk_steps + 2) * W);
+            path.assign(&inits[(size_t)a.r.init_index * W], &inits[(size_t)a.r.init_index * W] + W);
+            SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, e.stream_));
+            bound = ((u64)e.A_ + 2) * (a.r.surviving + 1);  // the stem and A + 1 segments, each a simple path
+            descend(rank.p, -1, 0);
+            s.stem_len = (int64_t)(path.size() / W - 1);
+            g = hw.last_idx;
+            if (g >= a.n) throw Error(SR_ERR_HIP, "liveness: the stem's last state has no arena index");
+            SR_HIP(hipMemcpy(&root, comp.p + g, sizeof(u32), hipMemcpyDeviceToHost));
+            if (root == ~0u) {
+                u64 all = 0;
+                for_each_successor(e.m_, &path[path.size() - W], [&](int, const u64*) { ++all; });
+                s.loop_len = 0;
+                e.live_accept(a.p, a.r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true);
+                return false;
+            }
+            if (root >= a.n) throw Error(SR_ERR_HIP, "liveness: the stem ends in a component without a root");
+            SR_HIP(hipMemcpy(c_mask, acc_me.p + (size_t)root * MW, sizeof(c_mask), hipMemcpyDeviceToHost));
+            return true;
+        }
+
+        // The closed walk inside g's component: for the slots in order the segment plan(slot) asks for (it reads
+        // hw.notme, hw.taken and c_mask; LIVE_PLAN_SKIP: none), then home to g. A segment is the target set
+        // (live_targets), ranks towards it inside the component, and the descent. keep_stem_masks: the weak
+        // mode's notme keeps what the stem recorded at g; the strong mode's masks are the loop's alone.
+        template <class Plan>
+        void closed_walk(Plan&& plan, bool keep_stem_masks, bool strong) {
+            lrank.alloc(e.o_.device, a.n);
+            SR_HIP(hipMemsetAsync(lrank.p, 0xff, (size_t)a.n * sizeof(u32), e.stream_));
+            if (keep_stem_masks) clear_head();
+            else SR_HIP(hipMemsetAsync(wc, 0, sizeof(LiveWeakCounters), e.stream_));
+            live_members<><<<blocks_for(a.np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(a.np, a.np_cnt, comp.p, root, Y, wc);
+            read_w();
+            const u32 mcnt = hw.next_n;
+            auto segment = [&](int pl, int slot) {
+                clear_head();
+                live_targets<M><<<blocks_for(mcnt, LIVE_BLOCK), LIVE_BLOCK, 0, e.stream_>>>(e.m_, e.arena_.p, a.t, idx.p, comp.p, root, pl, slot, g,
+                                                                                            Y, mcnt, lrank.p, L, wc);
+                read_w();
+                if (!hw.joined) throw Error(SR_ERR_NONDETERMINISM, "liveness: a segment of the closed walk has no target in its component");
+                reach(lrank.p, L, X, hw.next_n);
+                s.segments += 1;
+                descend(lrank.p, pl == LIVE_PLAN_TAKE ? slot : -1, 1);
+            };
+            for (int slot = 0; slot < (int)e.A_; ++slot) {
+                const int pl = plan(slot);
+                if (pl != LIVE_PLAN_SKIP) segment(pl, slot);
+            }
+            segment(LIVE_PLAN_HOME, 0);
+            s.loop_len = (int64_t)(path.size() / W - 1) - s.stem_len;
+            e.live_accept_loop(a.p, a.r, path, (size_t)s.stem_len, strong);
+        }
+    };
+
+    // The pass of the mode: only a FAIR_SLOTS model whose masks fit the kernels' counters has one.
+    void live_fair_pass(bool strong, const LivePassArgs& a) {
+        if constexpr (fair_slots_model<M> && M::MW <= LIVE_MW_MAX) {
+            if (strong) live_strong_pass(a, live_strong[a.p]);
+            else live_weak_pass(a, live_weak[a.p]);
         } else {
-            (void)p, (void)r, (void)sg, (void)n, (void)t, (void)bwords, (void)slot_of, (void)alive, (void)np, (void)np_cnt, (void)u0, (void)u0_cnt,
-                (void)spare, (void)inits, (void)k, (void)walk_steps;
-            throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
+            (void)a;
+            throw Error(SR_ERR_UNSUPPORTED, std::string(strong ? "strong" : "weak") + " fairness: this model's slots are not fairness classes");
         }
     }
 
-    // The weak mode's lasso, replayed on the host model before it becomes the discovery of p: every step is a
-    // successor in `actions()` order, the condition holds nowhere, no step returns its own state, the last
-    // state equals the state at loop_start word for word, and the loop is weakly fair on its own states and
-    // steps (live.hpp live_loop_fair). A path that fails is an engine error, never a discovery.
-    // strong (the strong mode's lasso): the loop is strongly fair instead (live_loop_strong_fair).
-    void live_accept_weak(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start, bool strong = false) {
-        if constexpr (fair_slots_model<M>) {
-            const size_t len = path.size() / W - 1;
-            const std::string name = m_.prop_name(p);
-            std::vector<i64> acts, described;
-            concrete_path(m_, path, acts, described);
-            for (size_t i = 0; i <= len; ++i)
-                if (!live_not_p(m_, p, &path[i * W]))
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
-            for (size_t i = 0; i < len; ++i)
-                if (std::equal(&path[i * W], &path[i * W] + W, &path[(i + 1) * W]))
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: step " + std::to_string(i) + " of the witness of \"" + name +
-                                                           "\" returns its own state (weak fairness steps over no self-loop)");
-            if (loop_start >= len || !std::equal(&path[len * W], &path[len * W] + W, &path[loop_start * W]))
-                throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" does not end where it starts");
-            if (strong ? !live_loop_strong_fair(m_, &path[loop_start * W], len - loop_start)
-                       : !live_loop_fair(m_, &path[loop_start * W], len - loop_start))
-                throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" is not " +
-                                                       (strong ? "strongly" : "weakly") + " fair");
-            r.loop_start = (int64_t)loop_start;
-            r.end_kind = SR_LIVE_END_LOOP;
-            r.witness_len = (int64_t)len;
-            live_path_[p] = path;
-            disc[p].found = true;
-            disc[p].level = disc[p].rank = 0;
+    // WEAK FAIRNESS: U trimmed, its components, per component the fairness accumulators (live_comp_acc), the
+    // goal set (live_goal), ranks towards it over F_p', and the witness.
+    void live_weak_pass(const LivePassArgs& a, sr_live_weak& wk) {
+        constexpr int MW = M::MW;
+        LiveFair<sr_live_weak> f(*this, a, wk);
+        f.setup();
+        f.trim();
+        wk.cyclic_states = f.cnt;
+        const bool cyclic = f.cnt != 0;  // (U is not empty iff F_p' has a cycle, iff there is a component)
+        if (cyclic) {
+            f.alloc_search();
+            SR_HIP(hipMemsetAsync(f.size.p, 0, (size_t)a.n * sizeof(u32), stream_));
+            SR_HIP(hipMemsetAsync(f.acc_me.p, 0xff, (size_t)a.n * MW * sizeof(u64), stream_));
+            SR_HIP(hipMemsetAsync(f.or_took.p, 0, (size_t)a.n * MW * sizeof(u64), stream_));
         }
+        f.components();
+        f.clear_head();
+        u32 sn = 0;
+        if (a.np_cnt) {
+            if (cyclic)  // (without a component live_goal reads none of size, and_me, or_took: comp is ~0 everywhere)
+                live_comp_acc<M><<<blocks_for(a.np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, a.t, f.idx.p, f.comp.p, a.np, a.np_cnt,
+                                                                                              f.size.p, f.acc_me.p, f.or_took.p, f.wc);
+            live_goal<M><<<blocks_for(a.np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(a.np, a.np_cnt, a.slot_of, a.alive, f.comp.p, f.size.p,
+                                                                                      f.acc_me.p, f.or_took.p, f.rank.p, f.L, f.wc);
+            f.read_w();
+            wk.components = f.hw.comps;
+            wk.fair_components = f.hw.fair_comps;
+            wk.goal_states = wk.fair_states = f.hw.goal;
+            sn = f.hw.next_n;
+        }
+        if (wk.goal_states) f.reach(f.rank.p, f.L, f.X, sn);
+        if (f.first_ranked() && f.stem())
+            f.closed_walk([&](int s) { return live_loop_plan(s, f.hw.notme, f.hw.taken, f.c_mask); }, true, false);
+        wk.pass_ms = secs(f.t0, Clock::now()) * 1e3;
     }
+
+    // STRONG FAIRNESS. The host form's recursive tree becomes level-synchronous rounds over all open components
+    // at once: W starts as the weak mode's U; a level takes the components of G'[W], accumulates or_me and
+    // or_took per component (live_comp_acc_or), lets live_refine freeze the fair nodes, drop the states that
+    // enable a bad slot and hand the rest back to W, and trims W again; until W is empty. Memory is the weak
+    // pass' plus one list of 4 bytes per state of N_p (the level's members); no level stamp is kept per state,
+    // because live_refine clears the component number of every state that is not frozen.
+    void live_strong_pass(const LivePassArgs& a, sr_live_strong& sg) {
+        constexpr int MW = M::MW;
+        LiveFair<sr_live_strong> f(*this, a, sg);
+        DBuf<u32> lvl;
+        f.setup();
+        f.trim();
+        sg.cyclic_states = f.cnt;
+        if (f.cnt) {
+            f.alloc_search();
+            lvl.alloc(o_.device, f.cnt);
+        }
+        u64 frozen = 0;
+        while (f.cnt) {  // one level of the tree
+            const u32 members = f.cnt;
+            SR_HIP(hipMemcpyAsync(lvl.p, f.L, (size_t)members * sizeof(u32), hipMemcpyDeviceToDevice, stream_));
+            live_level_open<MW><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(lvl.p, members, f.size.p, f.acc_me.p, f.or_took.p);
+            f.components();
+            // the level's components: accumulate, then freeze, drop or hand back every member
+            f.clear_head();
+            live_comp_acc_or<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, a.t, f.idx.p, f.comp.p, lvl.p, members,
+                                                                                            f.size.p, f.acc_me.p, f.or_took.p, f.wc);
+            live_refine<M><<<blocks_for(members, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, a.slot_of, lvl.p, members, f.comp.p, f.size.p,
+                                                                                       f.acc_me.p, f.or_took.p, f.bits.p, f.L, f.wc);
+            f.read_w();
+            if (f.hw.next_n >= members) throw Error(SR_ERR_HIP, "liveness: a level of the decomposition removed no state from W");
+            if (f.hw.comps) sg.levels += 1;
+            sg.components += f.hw.comps;
+            sg.fair_components += f.hw.fair_comps;
+            frozen += f.hw.joined;
+            f.cnt = f.hw.next_n;
+            if (o_.verbose)
+                std::fprintf(stderr, "[sr] liveness \"%s\" level %u: %u members, %u components (%u fair), %u back in W\n", m_.prop_name(a.p),
+                             sg.levels, members, f.hw.comps, f.hw.fair_comps, f.cnt);
+            f.trim();
+        }
+        // the goal set, ranks towards it over F_p'
+        f.clear_head();
+        u32 sn = 0;
+        if (a.np_cnt) {
+            live_goal_strong<><<<blocks_for(a.np_cnt, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(a.np, a.np_cnt, a.slot_of, a.alive, f.comp.p, f.rank.p,
+                                                                                            f.L, f.wc);
+            f.read_w();
+            sg.goal_states = sg.fair_states = f.hw.goal;
+            sn = f.hw.next_n;
+            if (f.hw.goal < frozen) throw Error(SR_ERR_HIP, "liveness: the goal set lost a frozen state");
+        }
+        if (sg.goal_states) f.reach(f.rank.p, f.L, f.X, sn);
+        if (f.first_ranked() && f.stem())
+            f.closed_walk([&](int s) { return live_strong_plan(s, f.hw.taken, f.c_mask); }, false, true);
+        sg.pass_ms = secs(f.t0, Clock::now()) * 1e3;
+    }
+
     std::vector<std::vector<u64>> live_path_;  // per property: the states of a discovery made by the liveness pass
 
     // Launch of the level whose frontier (n states) ends the arena, after the previous one is done:

@@ -115,6 +115,13 @@
 // (kernels_live.hpp: live_trim, live_walk) and the host form (live_host, the sr_liveness_host entry
 // point) instantiate; they differ only in how "is this successor in the set" is answered (the alive
 // bitmap by visited-set slot on the device, a hash map on the host).
+//
+// This file, in order: the per-state pieces shared with the kernels (live_step; for the fair modes live_moving,
+// live_descend_step, the *_masks and *_plan functions and the two loop-fairness checks); then, behind the
+// kernels' header, the host forms: LiveHostSet, live_host_fixpoint and live_host (plain and progress),
+// LiveHostGraph and live_host_fair_witness (what the weak and the strong form share), and live_host_weak and
+// live_host_strong, which hold their mode's decomposition only. The device's driver is in engine.hpp (live_pass,
+// LiveFair, live_weak_pass, live_strong_pass).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -314,18 +321,14 @@ bool live_loop_strong_fair(const M& m, const u64* states, size_t len) {
     return live_strong_masks<M::MW>(some, taken);
 }
 
-inline sr_live_strong live_strong_none() {
-    sr_live_strong s;
+// sr_live_weak and sr_live_strong name their fields alike (but reserved0 / levels), so what fills them is
+// written once, over the type.
+template <class Stats>
+Stats live_fair_none() {
+    Stats s;
     std::memset(&s, 0, sizeof(s));
     s.stem_len = s.loop_len = -1;
     return s;
-}
-
-inline sr_live_weak live_weak_none() {
-    sr_live_weak w;
-    std::memset(&w, 0, sizeof(w));
-    w.stem_len = w.loop_len = -1;
-    return w;
 }
 
 inline sr_live_result live_result_none() {
@@ -346,9 +349,14 @@ namespace sr {
 template <class M>
 std::vector<u64> init_states_of(const M& m);  // (engine.hpp)
 
-// The check on the host, with no device: a search over at most max_states states, the fixpoint (in
-// place, worklist by worklist as the device runs it) and the witness. FAIR: progress fairness; MOVES:
-// see live_step.
+// ---- The check on the host, with no device (the sr_liveness_host* entry points). The three forms are built
+// from pieces that are each written once: the reachable set (LiveHostSet), the fixpoint (live_host_fixpoint),
+// and for the weak and the strong form the graph G' with its |U| count, Tarjan's algorithm and breadth-first
+// ranks (LiveHostGraph) and the witness (live_host_fair_witness: the stem, the sink ending, the closed walk).
+// The fair forms deliberately run other algorithms than the device's (Tarjan and predecessor lists against
+// colouring rounds); only the per-state pieces above (live_step, live_moving, live_descend_step, the *_masks
+// and *_plan functions) are the kernels'.
+
 struct LiveHost {
     sr_live_result r = live_result_none();
     u64 unique = 0;
@@ -356,11 +364,17 @@ struct LiveHost {
     std::vector<i64> actions;  // its canonical action ids, one per step
 };
 
-template <bool FAIR = false, bool MOVES = true, class M>
-LiveHost live_host(const M& m, int p, u64 max_states) {
-    constexpr int W = M::W;
-    if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
-        throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
+template <class Stats>  // sr_live_weak or sr_live_strong
+struct LiveHostFair {
+    LiveHost h;
+    Stats s = live_fair_none<Stats>();
+};
+
+// The reachable set: a search over at most max_states states, which numbers them in the order it finds
+// them. Refuses a p that is no `eventually` property.
+template <class M>
+struct LiveHostSet {
+    static constexpr int W = M::W;
     struct H {
         size_t operator()(const std::vector<u64>& v) const {
             u64 h = 0;
@@ -368,10 +382,23 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
             return (size_t)h;
         }
     };
-    const auto t0 = std::chrono::steady_clock::now();
+    const M& m;
+    const u64 max_states;
     std::unordered_map<std::vector<u64>, u32, H> index;
     std::vector<std::vector<u64>> st;
-    auto add = [&](const u64* s) {
+    std::vector<u32> init_idx;  // the init states' numbers, in the order of `init_states`
+
+    LiveHostSet(const M& m_, int p, u64 max_states_) : m(m_), max_states(max_states_) {
+        if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
+            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
+        const std::vector<u64> inits = init_states_of(m);
+        for (size_t i = 0; i < inits.size() / W; ++i) init_idx.push_back(add(&inits[i * W]));
+        for (size_t q = 0; q < st.size(); ++q) {
+            const std::vector<u64> s = st[q];  // (a copy: add() grows st)
+            for_each_successor(m, s.data(), [&](int, const u64* ns) { add(ns); });
+        }
+    }
+    u32 add(const u64* s) {
         std::vector<u64> v(s, s + W);
         auto it = index.find(v);
         if (it != index.end()) return it->second;
@@ -381,53 +408,61 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
         index.emplace(v, i);
         st.push_back(std::move(v));
         return i;
-    };
-    const std::vector<u64> inits = init_states_of(m);
-    const int k = (int)(inits.size() / W);
-    std::vector<u32> init_idx;
-    for (int i = 0; i < k; ++i) init_idx.push_back(add(&inits[(size_t)i * W]));
-    for (size_t q = 0; q < st.size(); ++q) {
-        const std::vector<u64> s = st[q];  // (a copy: add() grows st)
-        for_each_successor(m, s.data(), [&](int, const u64* ns) { add(ns); });
     }
-    LiveHost h;
-    h.unique = st.size();
-    h.r.ran = 1;
-    std::vector<char> alive(st.size(), 0);
-    std::vector<u32> wl, next;
-    for (u32 i = 0; i < (u32)st.size(); ++i)
-        if (live_not_p(m, p, st[i].data())) {
-            alive[i] = 1;
-            wl.push_back(i);
-        }
-    h.r.not_p_states = h.r.surviving = wl.size();
-    auto is_alive = [&](const u64* ns) {
+    u32 find(const u64* ns) const {
         auto it = index.find(std::vector<u64>(ns, ns + W));
         if (it == index.end()) throw Error(SR_ERR_NONDETERMINISM, "liveness: a successor of a reachable state is not in the reachable set");
-        return alive[it->second] != 0;
-    };
-    u64 out[W];
+        return it->second;
+    }
+};
+
+// The fixpoint over R (in place, worklist by worklist as the device runs it): fills r's counters and returns
+// the alive vector, F_p (FAIR: F_p'). FAIR: progress fairness; MOVES: see live_step.
+template <bool FAIR, bool MOVES, class M>
+std::vector<char> live_host_fixpoint(const LiveHostSet<M>& R, int p, sr_live_result& r) {
+    std::vector<char> alive(R.st.size(), 0);
+    std::vector<u32> wl, next;
+    for (u32 i = 0; i < (u32)R.st.size(); ++i)
+        if (live_not_p(R.m, p, R.st[i].data())) alive[i] = 1, wl.push_back(i);
+    r.not_p_states = r.surviving = wl.size();
+    auto is_alive = [&](const u64* ns) { return alive[R.find(ns)] != 0; };
+    u64 out[M::W];
     for (;;) {
         u64 removed = 0;
         next.clear();
-        h.r.rounds += 1;
-        h.r.examined += wl.size();
+        r.rounds += 1;
+        r.examined += wl.size();
         for (u32 i : wl) {
-            const int a = live_step<FAIR, MOVES>(m, st[i].data(), is_alive, out);
+            const int a = live_step<FAIR, MOVES>(R.m, R.st[i].data(), is_alive, out);
             if (a >= 0) next.push_back(i);
             else if (a == LIVE_DEAD) alive[i] = 0, ++removed;
         }
         wl.swap(next);
-        h.r.surviving -= removed;
+        r.surviving -= removed;
         if (!removed) break;
     }
-    for (int i = 0; i < k && h.r.init_index < 0; ++i)
-        if (alive[init_idx[i]]) h.r.init_index = i;
+    return alive;
+}
+
+// The plain and the progress form: the reachable set, the fixpoint and the witness.
+template <bool FAIR = false, bool MOVES = true, class M>
+LiveHost live_host(const M& m, int p, u64 max_states) {
+    constexpr int W = M::W;
+    const auto t0 = std::chrono::steady_clock::now();
+    const LiveHostSet<M> R(m, p, max_states);
+    LiveHost h;
+    h.unique = R.st.size();
+    h.r.ran = 1;
+    const std::vector<char> alive = live_host_fixpoint<FAIR, MOVES>(R, p, h.r);
+    for (size_t i = 0; i < R.init_idx.size() && h.r.init_index < 0; ++i)
+        if (alive[R.init_idx[i]]) h.r.init_index = (int32_t)i;
     if (h.r.init_index >= 0) {
+        auto is_alive = [&](const u64* ns) { return alive[R.find(ns)] != 0; };
         std::unordered_map<u32, i64> at;  // state -> its position on the path
-        u32 cur = init_idx[h.r.init_index];
+        u32 cur = R.init_idx[h.r.init_index];
+        u64 out[W];
         for (i64 t = 0;; ++t) {
-            h.words.insert(h.words.end(), st[cur].begin(), st[cur].end());
+            h.words.insert(h.words.end(), R.st[cur].begin(), R.st[cur].end());
             auto seen = at.find(cur);
             if (seen != at.end()) {
                 h.r.witness_len = t;
@@ -436,619 +471,380 @@ LiveHost live_host(const M& m, int p, u64 max_states) {
                 break;
             }
             at.emplace(cur, t);
-            const int a = live_step<FAIR, MOVES>(m, st[cur].data(), is_alive, out);
+            const int a = live_step<FAIR, MOVES>(m, R.st[cur].data(), is_alive, out);
             if (a == LIVE_TERMINAL || a == LIVE_STUTTER) {
                 h.r.witness_len = t;
                 h.r.end_kind = a == LIVE_TERMINAL ? SR_LIVE_END_TERMINAL : SR_LIVE_END_STUTTER;
                 break;
             }
             if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a state of the fixpoint has no successor in it");
-            h.actions.push_back(m.action_id(st[cur].data(), a));
-            cur = index.at(std::vector<u64>(out, out + W));
+            h.actions.push_back(m.action_id(R.st[cur].data(), a));
+            cur = R.find(out);
         }
     }
     h.r.pass_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return h;
 }
 
-// The check under WEAK FAIRNESS on the host, with no device, by other algorithms than the device's:
-// the host search and the progress fixpoint as live_host runs them, then Tarjan's algorithm
-// (iterative) for the components of G', breadth-first ranks over predecessor lists, and the witness
-// rule of the header. The per-state pieces (live_moving, live_fair_masks, live_descend_step,
-// live_loop_plan) are the kernels'.
-struct LiveHostWeak {
-    LiveHost h;
-    sr_live_weak w = live_weak_none();
-};
+// G': the states of F_p' (numbered by `pos`), their succ' edges to other states of F_p', the predecessors, the
+// me masks and the sinks; with what both fair forms run on it.
+template <bool MOVES, class M>
+struct LiveHostGraph {
+    static constexpr int MW = M::MW;
+    static constexpr u32 NONE = ~0u;
+    struct Edge {
+        u32 a, t;
+    };
+    const LiveHostSet<M>& R;
+    std::vector<u32> fs, pos;
+    u32 nf = 0;
+    std::vector<std::vector<Edge>> out_e;
+    std::vector<std::vector<u32>> preds;
+    std::vector<u64> me;  // MW words per state
+    std::vector<char> sink;
 
-template <bool MOVES = true, class M>
-LiveHostWeak live_host_weak(const M& m, int p, u64 max_states) {
-    constexpr int W = M::W, MW = M::MW;
-    constexpr u32 NONE = ~0u;
-    if constexpr (!fair_slots_model<M>) {
-        throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
-    } else {
-        if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
-            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
-        struct H {
-            size_t operator()(const std::vector<u64>& v) const {
-                u64 h = 0;
-                for (u64 x : v) h = fmix64(h ^ x) + 0x9E3779B97F4A7C15ull;
-                return (size_t)h;
-            }
-        };
-        const auto t0 = std::chrono::steady_clock::now();
-        std::unordered_map<std::vector<u64>, u32, H> index;
-        std::vector<std::vector<u64>> st;
-        auto add = [&](const u64* s) {
-            std::vector<u64> v(s, s + W);
-            auto it = index.find(v);
-            if (it != index.end()) return it->second;
-            if (st.size() >= max_states)
-                throw Error(SR_ERR_CAPACITY, "liveness: the model has more than " + std::to_string(max_states) + " reachable states (max_states)");
-            const u32 i = (u32)st.size();
-            index.emplace(v, i);
-            st.push_back(std::move(v));
-            return i;
-        };
-        const std::vector<u64> inits = init_states_of(m);
-        const int k = (int)(inits.size() / W);
-        std::vector<u32> init_idx;
-        for (int i = 0; i < k; ++i) init_idx.push_back(add(&inits[(size_t)i * W]));
-        for (size_t q = 0; q < st.size(); ++q) {
-            const std::vector<u64> s = st[q];  // (a copy: add() grows st)
-            for_each_successor(m, s.data(), [&](int, const u64* ns) { add(ns); });
-        }
-        LiveHostWeak res;
-        LiveHost& h = res.h;
-        sr_live_weak& wk = res.w;
-        h.unique = st.size();
-        h.r.ran = wk.ran = 1;
-        auto find = [&](const u64* ns) {
-            auto it = index.find(std::vector<u64>(ns, ns + W));
-            if (it == index.end()) throw Error(SR_ERR_NONDETERMINISM, "liveness: a successor of a reachable state is not in the reachable set");
-            return it->second;
-        };
-        // the progress fixpoint, as live_host<true> runs it
-        std::vector<char> alive(st.size(), 0);
-        {
-            std::vector<u32> wl, next;
-            for (u32 i = 0; i < (u32)st.size(); ++i)
-                if (live_not_p(m, p, st[i].data())) alive[i] = 1, wl.push_back(i);
-            h.r.not_p_states = h.r.surviving = wl.size();
-            auto is_alive = [&](const u64* ns) { return alive[find(ns)] != 0; };
-            u64 out[W];
-            for (;;) {
-                u64 removed = 0;
-                next.clear();
-                h.r.rounds += 1;
-                h.r.examined += wl.size();
-                for (u32 i : wl) {
-                    const int a = live_step<true, MOVES>(m, st[i].data(), is_alive, out);
-                    if (a >= 0) next.push_back(i);
-                    else if (a == LIVE_DEAD) alive[i] = 0, ++removed;
-                }
-                wl.swap(next);
-                h.r.surviving -= removed;
-                if (!removed) break;
-            }
-        }
-        const auto t1 = std::chrono::steady_clock::now();
-        // G': the states of F_p' (numbered by `pos`), their edges to other states of F_p', predecessors
-        std::vector<u32> fs, pos(st.size(), NONE);
-        for (u32 i = 0; i < (u32)st.size(); ++i)
+    LiveHostGraph(const LiveHostSet<M>& R_, const std::vector<char>& alive) : R(R_), pos(R_.st.size(), NONE) {
+        for (u32 i = 0; i < (u32)R.st.size(); ++i)
             if (alive[i]) pos[i] = (u32)fs.size(), fs.push_back(i);
-        const u32 nf = (u32)fs.size();
-        struct Edge {
-            u32 a, t;
-        };
-        std::vector<std::vector<Edge>> out_e(nf);
-        std::vector<std::vector<u32>> preds(nf);
-        std::vector<u64> me((size_t)nf * MW);
-        std::vector<char> sink(nf, 0);
+        nf = (u32)fs.size();
+        out_e.resize(nf), preds.resize(nf), me.resize((size_t)nf * MW), sink.assign(nf, 0);
+        num.resize(nf), low.resize(nf), next_e.resize(nf), on.assign(nf, 0);
         for (u32 v = 0; v < nf; ++v) {
-            live_moving<MOVES>(m, st[fs[v]].data(), &me[(size_t)v * MW], [&](int a, const u64* ns) {
-                const u32 t = pos[find(ns)];
+            live_moving<MOVES>(R.m, state(v), &me[(size_t)v * MW], [&](int a, const u64* ns) {
+                const u32 t = at(ns);
                 if (t != NONE) out_e[v].push_back({(u32)a, t}), preds[t].push_back(v);
             });
             bool any = false;
             for (int w = 0; w < MW; ++w) any = any || me[(size_t)v * MW + w];
             sink[v] = !any;
         }
-        // |U|: F_p' without its sinks, trimmed to the states with a successor in it
-        {
-            std::vector<char> in_u(nf);
-            std::vector<u32> cnt(nf, 0), todo;
-            for (u32 v = 0; v < nf; ++v) in_u[v] = !sink[v];
-            for (u32 v = 0; v < nf; ++v) {
-                for (const Edge& e : out_e[v]) cnt[v] += in_u[e.t];
-                if (in_u[v] && !cnt[v]) todo.push_back(v);
-            }
-            while (!todo.empty()) {
-                const u32 v = todo.back();
-                todo.pop_back();
-                in_u[v] = 0;
-                for (u32 q : preds[v])
-                    if (in_u[q] && --cnt[q] == 0) todo.push_back(q);
-            }
-            for (u32 v = 0; v < nf; ++v) wk.cyclic_states += in_u[v];
+    }
+    const u64* state(u32 v) const { return R.st[fs[v]].data(); }
+    u32 at(const u64* ns) const { return pos[R.find(ns)]; }  // (NONE: a reachable state outside F_p')
+    bool moving(u32 v, int a) const { return me[(size_t)v * MW + (a >> 6)] >> (a & 63) & 1; }
+
+    // |U|: F_p' without its sinks, trimmed to the states with a successor in it
+    u64 cyclic_states() const {
+        std::vector<char> in_u(nf);
+        std::vector<u32> cnt(nf, 0), todo;
+        for (u32 v = 0; v < nf; ++v) in_u[v] = !sink[v];
+        for (u32 v = 0; v < nf; ++v) {
+            for (const Edge& e : out_e[v]) cnt[v] += in_u[e.t];
+            if (in_u[v] && !cnt[v]) todo.push_back(v);
         }
-        // Tarjan, iterative: comp[v] = the component's number for a component of two or more states
-        std::vector<u32> comp(nf, NONE);
-        std::vector<std::vector<u32>> members;
-        {
-            std::vector<u32> num(nf, NONE), low(nf, 0), stack, at(nf, 0);
-            std::vector<char> on(nf, 0);
-            std::vector<u32> call;
-            u32 counter = 0;
-            for (u32 root = 0; root < nf; ++root) {
-                if (num[root] != NONE) continue;
-                call.push_back(root);
-                while (!call.empty()) {
-                    const u32 v = call.back();
-                    if (num[v] == NONE) num[v] = low[v] = counter++, stack.push_back(v), on[v] = 1;
-                    bool down = false;
-                    while (at[v] < out_e[v].size()) {
-                        const u32 t = out_e[v][at[v]].t;
+        while (!todo.empty()) {
+            const u32 v = todo.back();
+            todo.pop_back();
+            in_u[v] = 0;
+            for (u32 q : preds[v])
+                if (in_u[q] && --cnt[q] == 0) todo.push_back(q);
+        }
+        u64 n = 0;
+        for (u32 v = 0; v < nf; ++v) n += in_u[v];
+        return n;
+    }
+
+    // Tarjan, iterative, on G'[X]: X the vertices `verts` (roots are tried in that order), in(t) whether t is
+    // in X. Every component of two or more states goes to f(c) (c may be moved from), in the order found.
+    template <class In, class F>
+    void components(const std::vector<u32>& verts, In&& in, F&& f) {
+        for (u32 v : verts) num[v] = NONE, next_e[v] = 0;
+        u32 counter = 0;
+        for (u32 root : verts) {
+            if (num[root] != NONE) continue;
+            call.push_back(root);
+            while (!call.empty()) {
+                const u32 v = call.back();
+                if (num[v] == NONE) num[v] = low[v] = counter++, stack.push_back(v), on[v] = 1;
+                bool down = false;
+                while (next_e[v] < out_e[v].size()) {
+                    const u32 t = out_e[v][next_e[v]].t;
+                    if (in(t)) {
                         if (num[t] == NONE) {
                             call.push_back(t);
                             down = true;
                             break;
                         }
                         if (on[t]) low[v] = std::min(low[v], num[t]);
-                        ++at[v];
                     }
-                    if (down) continue;
-                    call.pop_back();
-                    if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[v]);
-                    if (low[v] == num[v]) {
-                        std::vector<u32> c;
-                        for (;;) {
-                            const u32 x = stack.back();
-                            stack.pop_back();
-                            on[x] = 0;
-                            c.push_back(x);
-                            if (x == v) break;
-                        }
-                        if (c.size() >= 2) {
-                            for (u32 x : c) comp[x] = (u32)members.size();
-                            members.push_back(std::move(c));
-                        }
-                    }
+                    ++next_e[v];
                 }
-            }
-        }
-        wk.components = members.size();
-        std::vector<u64> and_me(members.size() * MW, ~0ull), or_took(members.size() * MW, 0);
-        for (u32 v = 0; v < nf; ++v) {
-            if (comp[v] == NONE) continue;
-            for (int w = 0; w < MW; ++w) and_me[(size_t)comp[v] * MW + w] &= me[(size_t)v * MW + w];
-            for (const Edge& e : out_e[v])
-                if (comp[e.t] == comp[v]) or_took[(size_t)comp[v] * MW + (e.a >> 6)] |= 1ull << (e.a & 63);
-        }
-        std::vector<char> fair(members.size(), 0);
-        for (size_t c = 0; c < members.size(); ++c) {
-            fair[c] = live_fair_masks<MW>(&and_me[c * MW], &or_took[c * MW]);
-            wk.fair_components += fair[c];
-        }
-        // breadth-first ranks towards `targets` over the predecessors inside a domain (dom(v))
-        auto ranks_to = [&](const std::vector<u32>& targets, auto&& dom, std::vector<u32>& rank) -> u32 {
-            std::vector<u32> level = targets, nxt;
-            for (u32 v : targets) rank[v] = 0;
-            u32 rounds = 0;
-            for (u32 r = 1; !level.empty(); ++r, ++rounds) {
-                nxt.clear();
-                for (u32 t : level)
-                    for (u32 q : preds[t])
-                        if (dom(q) && rank[q] == NONE) rank[q] = r, nxt.push_back(q);
-                level.swap(nxt);
-            }
-            return rounds;
-        };
-        std::vector<u32> rank(nf, NONE), goal;
-        for (u32 v = 0; v < nf; ++v)
-            if (sink[v] || (comp[v] != NONE && fair[comp[v]])) goal.push_back(v);
-        wk.goal_states = goal.size();
-        wk.reach_rounds += ranks_to(goal, [](u32) { return true; }, rank);
-        for (u32 v = 0; v < nf; ++v) wk.fair_states += rank[v] != NONE;
-        for (int i = 0; i < k && h.r.init_index < 0; ++i)
-            if (alive[init_idx[i]] && rank[pos[init_idx[i]]] != NONE) h.r.init_index = i;
-        if (h.r.init_index >= 0) {
-            u64 notme[MW] = {}, taken[MW] = {};
-            u32 cur = pos[init_idx[h.r.init_index]];
-            h.words.assign(st[fs[cur]].begin(), st[fs[cur]].end());
-            // follows the lowest rank-decreasing slot from cur to rank 0, then takes slot `then` (if >= 0)
-            auto walk = [&](const std::vector<u32>& rk, int then, bool all) {
-                u64 mk[MW], nx[W];
-                auto step_to = [&](int a) {
-                    h.actions.push_back(m.action_id(st[fs[cur]].data(), a));
-                    cur = pos[find(nx)];
-                    if (cur == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness leaves F_p'");
-                    h.words.insert(h.words.end(), nx, nx + W);
-                };
+                if (down) continue;
+                call.pop_back();
+                if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[v]);
+                if (low[v] != num[v]) continue;
+                std::vector<u32> c;
                 for (;;) {
-                    const u32 r = rk[cur];
-                    if (r == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is at a state without a rank");
-                    const int a = live_descend_step<MOVES>(
-                        m, st[fs[cur]].data(), r,
-                        [&](const u64* ns) {
-                            const u32 t = pos[find(ns)];
-                            return t == NONE ? NONE : rk[t];
-                        },
-                        mk, nx);
-                    if (all || !r)
-                        for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
-                    if (!r) break;
-                    if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state has no successor of a lower rank");
-                    if (all) taken[a >> 6] |= 1ull << (a & 63);
-                    step_to(a);
+                    const u32 x = stack.back();
+                    stack.pop_back();
+                    on[x] = 0;
+                    c.push_back(x);
+                    if (x == v) break;
                 }
-                if (then >= 0) {
-                    if (!m.apply(st[fs[cur]].data(), then, nx)) throw Error(SR_ERR_NONDETERMINISM, "liveness: the slot to take is refused");
-                    taken[then >> 6] |= 1ull << (then & 63);
-                    step_to(then);
-                    live_moving<MOVES>(m, st[fs[cur]].data(), mk, [](int, const u64*) {});
-                    for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
-                }
-            };
-            walk(rank, -1, false);
-            wk.stem_len = (int64_t)h.actions.size();
-            const u32 g = cur;
-            if (sink[g]) {
-                u64 all = 0;
-                for_each_successor(m, st[fs[g]].data(), [&](int, const u64*) { ++all; });
-                h.r.end_kind = all ? SR_LIVE_END_STUTTER : SR_LIVE_END_TERMINAL;
-                wk.loop_len = 0;
-            } else {
-                const u32 c = comp[g];
-                if (c == NONE || !fair[c]) throw Error(SR_ERR_NONDETERMINISM, "liveness: the stem ends outside every fair component");
-                std::vector<u32> lrank(nf, NONE), targets;
-                auto in_c = [&](u32 v) { return comp[v] == c; };
-                auto segment = [&](int then) {
-                    for (u32 v : members[c]) lrank[v] = NONE;
-                    wk.reach_rounds += ranks_to(targets, in_c, lrank);
-                    wk.segments += 1;
-                    walk(lrank, then, true);
-                };
-                for (int a = 0; a < m.max_actions(); ++a) {
-                    const int plan = live_loop_plan(a, notme, taken, &and_me[(size_t)c * MW]);
-                    if (plan == LIVE_PLAN_SKIP) continue;
-                    targets.clear();
-                    for (u32 v : members[c]) {
-                        const bool mv = me[(size_t)v * MW + (a >> 6)] >> (a & 63) & 1;
-                        bool hit = plan == LIVE_PLAN_NOTME && !mv;
-                        if (plan == LIVE_PLAN_TAKE && mv)
-                            for (const Edge& e : out_e[v]) hit = hit || ((int)e.a == a && comp[e.t] == c);
-                        if (hit) targets.push_back(v);
-                    }
-                    segment(plan == LIVE_PLAN_TAKE ? a : -1);
-                }
-                targets.assign(1, g);
-                segment(-1);
-                h.r.end_kind = SR_LIVE_END_LOOP;
-                h.r.loop_start = wk.stem_len;
-                wk.loop_len = (int64_t)h.actions.size() - wk.stem_len;
-                if (!live_loop_fair(m, &h.words[(size_t)wk.stem_len * W], (size_t)wk.loop_len))
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness is not weakly fair");
+                if (c.size() >= 2) f(c);
             }
-            h.r.witness_len = (int64_t)h.actions.size();
         }
+    }
+
+    // breadth-first ranks towards `targets` over the predecessors inside a domain (dom(v)); the levels it took
+    template <class Dom>
+    u32 ranks_to(const std::vector<u32>& targets, Dom&& dom, std::vector<u32>& rank) const {
+        std::vector<u32> level = targets, nxt;
+        for (u32 v : targets) rank[v] = 0;
+        u32 rounds = 0;
+        for (u32 r = 1; !level.empty(); ++r, ++rounds) {
+            nxt.clear();
+            for (u32 t : level)
+                for (u32 q : preds[t])
+                    if (dom(q) && rank[q] == NONE) rank[q] = r, nxt.push_back(q);
+            level.swap(nxt);
+        }
+        return rounds;
+    }
+
+private:
+    std::vector<u32> num, low, next_e, stack, call;  // Tarjan's scratch, kept across calls
+    std::vector<char> on;
+};
+
+// What differs between the two fair forms' witnesses: how the closed walk plans slot a from the loop's masks
+// so far and the component's accumulator (and_me of a fair component, or_me of a fair node), whether the
+// walk records notme at all, and the fairness the finished loop is checked for.
+struct LiveWeakWalk {
+    static constexpr bool NOTME = true;
+    static constexpr const char* NAME = "weak fairness";
+    static constexpr const char* FAIR = "weakly";
+    static int plan(int a, const u64* notme, const u64* taken, const u64* and_me) { return live_loop_plan(a, notme, taken, and_me); }
+    template <class M>
+    static bool loop_fair(const M& m, const u64* states, size_t len) {
+        return live_loop_fair(m, states, len);
+    }
+};
+struct LiveStrongWalk {
+    static constexpr bool NOTME = false;
+    static constexpr const char* NAME = "strong fairness";
+    static constexpr const char* FAIR = "strongly";
+    static int plan(int a, const u64*, const u64* taken, const u64* or_me) { return live_strong_plan(a, taken, or_me); }
+    template <class M>
+    static bool loop_fair(const M& m, const u64* states, size_t len) {
+        return live_loop_strong_fair(m, states, len);
+    }
+};
+
+// The goal set, FairF and the witness rule of the header, given the decomposition: node[v] the fair component
+// (fair node) of v or NONE, members and masks (MW words: Walk::plan's accumulator) by that number. The stem,
+// then the sink ending, or the closed walk inside g's component: per slot the plan, the target set (NOTME: the
+// members with !me(., a); TAKE: those whose a-step stays inside), ranks towards it inside the component, the
+// walk; then home to g.
+template <class Walk, bool MOVES, class M, class Stats>
+void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<u32>& node, const std::vector<std::vector<u32>>& members,
+                            const std::vector<u64>& masks, LiveHost& h, Stats& s) {
+    constexpr int W = M::W, MW = M::MW;
+    constexpr u32 NONE = ~0u;
+    const M& m = G.R.m;
+    std::vector<u32> rank(G.nf, NONE), goal;
+    for (u32 v = 0; v < G.nf; ++v)
+        if (G.sink[v] || node[v] != NONE) goal.push_back(v);
+    s.goal_states = goal.size();
+    s.reach_rounds += G.ranks_to(goal, [](u32) { return true; }, rank);
+    for (u32 v = 0; v < G.nf; ++v) s.fair_states += rank[v] != NONE;
+    const std::vector<u32>& init_idx = G.R.init_idx;
+    for (size_t i = 0; i < init_idx.size() && h.r.init_index < 0; ++i)
+        if (G.pos[init_idx[i]] != NONE && rank[G.pos[init_idx[i]]] != NONE) h.r.init_index = (int32_t)i;
+    if (h.r.init_index < 0) return;
+    u64 notme[MW] = {}, taken[MW] = {}, mk[MW], nx[W];
+    u32 cur = G.pos[init_idx[h.r.init_index]];
+    h.words.assign(G.state(cur), G.state(cur) + W);
+    auto step_to = [&](int a, bool loop) {  // the step by slot a, whose successor is in nx
+        h.actions.push_back(m.action_id(G.state(cur), a));
+        if (loop) taken[a >> 6] |= 1ull << (a & 63);
+        cur = G.at(nx);
+        if (cur == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness leaves F_p'");
+        h.words.insert(h.words.end(), nx, nx + W);
+    };
+    // follows the lowest rank-lowering slot from cur to rank 0, then takes slot `then` (if >= 0). loop (a segment
+    // of the closed walk, not the stem): the steps count as taken, and with Walk::NOTME every state passed adds
+    // to notme; the stem adds only its last state, g.
+    auto walk = [&](const std::vector<u32>& rk, int then, bool loop) {
+        for (;;) {
+            const u32 r = rk[cur];
+            if (r == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is at a state without a rank");
+            if (!r && !Walk::NOTME) break;
+            const int a = live_descend_step<MOVES>(
+                m, G.state(cur), r,
+                [&](const u64* ns) {
+                    const u32 t = G.at(ns);
+                    return t == NONE ? NONE : rk[t];
+                },
+                mk, nx);
+            if (Walk::NOTME && (loop || !r))
+                for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
+            if (!r) break;
+            if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state has no successor of a lower rank");
+            step_to(a, loop);
+        }
+        if (then >= 0) {
+            if (!m.apply(G.state(cur), then, nx)) throw Error(SR_ERR_NONDETERMINISM, "liveness: the slot to take is refused");
+            step_to(then, true);
+            if (Walk::NOTME) {
+                live_moving<MOVES>(m, G.state(cur), mk, [](int, const u64*) {});
+                for (int w = 0; w < MW; ++w) notme[w] |= ~mk[w];
+            }
+        }
+    };
+    walk(rank, -1, false);
+    s.stem_len = (int64_t)h.actions.size();
+    const u32 g = cur;
+    if (G.sink[g]) {
+        u64 all = 0;
+        for_each_successor(m, G.state(g), [&](int, const u64*) { ++all; });
+        h.r.end_kind = all ? SR_LIVE_END_STUTTER : SR_LIVE_END_TERMINAL;
+        s.loop_len = 0;
+    } else {
+        const u32 c = node[g];
+        if (c == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the stem ends outside every fair component");
+        std::vector<u32> lrank(G.nf, NONE), targets;
+        auto segment = [&](int then) {
+            for (u32 v : members[c]) lrank[v] = NONE;
+            s.reach_rounds += G.ranks_to(targets, [&](u32 v) { return node[v] == c; }, lrank);
+            s.segments += 1;
+            walk(lrank, then, true);
+        };
+        for (int a = 0; a < m.max_actions(); ++a) {
+            const int plan = Walk::plan(a, notme, taken, &masks[(size_t)c * MW]);
+            if (plan == LIVE_PLAN_SKIP) continue;
+            targets.clear();
+            for (u32 v : members[c]) {
+                bool hit = plan == LIVE_PLAN_NOTME && !G.moving(v, a);
+                if (plan == LIVE_PLAN_TAKE && G.moving(v, a))
+                    for (const auto& e : G.out_e[v]) hit = hit || ((int)e.a == a && node[e.t] == c);
+                if (hit) targets.push_back(v);
+            }
+            segment(plan == LIVE_PLAN_TAKE ? a : -1);
+        }
+        targets.assign(1, g);
+        segment(-1);
+        h.r.end_kind = SR_LIVE_END_LOOP;
+        h.r.loop_start = s.stem_len;
+        s.loop_len = (int64_t)h.actions.size() - s.stem_len;
+        if (!Walk::loop_fair(m, &h.words[(size_t)s.stem_len * W], (size_t)s.loop_len))
+            throw Error(SR_ERR_NONDETERMINISM, std::string("liveness: the closed walk of the witness is not ") + Walk::FAIR + " fair");
+    }
+    h.r.witness_len = (int64_t)h.actions.size();
+}
+
+// A fair form: the host search and the progress fixpoint as live_host<true> runs them, G' and |U|, the mode's
+// decomposition (decompose(G, s, node, members, masks): see live_host_fair_witness), the witness, the times.
+template <class Walk, class Stats, bool MOVES, class M, class Decompose>
+LiveHostFair<Stats> live_host_fair(const M& m, int p, u64 max_states, Decompose&& decompose) {
+    if constexpr (!fair_slots_model<M>) {
+        throw Error(SR_ERR_UNSUPPORTED, std::string(Walk::NAME) + ": this model's slots are not fairness classes");
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        const LiveHostSet<M> R(m, p, max_states);
+        LiveHostFair<Stats> res;
+        res.h.unique = R.st.size();
+        res.h.r.ran = res.s.ran = 1;
+        const std::vector<char> alive = live_host_fixpoint<true, MOVES>(R, p, res.h.r);
+        const auto t1 = std::chrono::steady_clock::now();
+        LiveHostGraph<MOVES, M> G(R, alive);
+        res.s.cyclic_states = G.cyclic_states();
+        std::vector<u32> node(G.nf, ~0u);
+        std::vector<std::vector<u32>> members;
+        std::vector<u64> masks;
+        decompose(G, res.s, node, members, masks);
+        live_host_fair_witness<Walk>(G, node, members, masks, res.h, res.s);
         const auto t2 = std::chrono::steady_clock::now();
-        h.r.pass_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
-        wk.pass_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+        res.h.r.pass_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
+        res.s.pass_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
         return res;
     }
 }
 
-// The check under STRONG FAIRNESS on the host, with no device, deliberately by another algorithm than the
-// device's level-synchronous rounds: the host search and the progress fixpoint as live_host runs them, then
-// the decomposition tree component by component (a work stack of vertex sets, Tarjan's algorithm on each),
-// breadth-first ranks over predecessor lists, and the witness rule of the header. Only the per-state pieces
-// (live_moving, live_strong_masks, live_descend_step, live_strong_plan) are the kernels'.
-struct LiveHostStrong {
-    LiveHost h;
-    sr_live_strong s = live_strong_none();
-};
-
+// WEAK FAIRNESS on the host: the maximal components of G' (one Tarjan over everything), their and_me and
+// or_took accumulators and live_fair_masks; the fair ones are the witness' components.
 template <bool MOVES = true, class M>
-LiveHostStrong live_host_strong(const M& m, int p, u64 max_states) {
-    constexpr int W = M::W, MW = M::MW;
-    constexpr u32 NONE = ~0u;
-    if constexpr (!fair_slots_model<M>) {
-        throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
-    } else {
-        if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
-            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
-        struct H {
-            size_t operator()(const std::vector<u64>& v) const {
-                u64 h = 0;
-                for (u64 x : v) h = fmix64(h ^ x) + 0x9E3779B97F4A7C15ull;
-                return (size_t)h;
-            }
-        };
-        const auto t0 = std::chrono::steady_clock::now();
-        std::unordered_map<std::vector<u64>, u32, H> index;
-        std::vector<std::vector<u64>> st;
-        auto add = [&](const u64* s) {
-            std::vector<u64> v(s, s + W);
-            auto it = index.find(v);
-            if (it != index.end()) return it->second;
-            if (st.size() >= max_states)
-                throw Error(SR_ERR_CAPACITY, "liveness: the model has more than " + std::to_string(max_states) + " reachable states (max_states)");
-            const u32 i = (u32)st.size();
-            index.emplace(v, i);
-            st.push_back(std::move(v));
-            return i;
-        };
-        const std::vector<u64> inits = init_states_of(m);
-        const int k = (int)(inits.size() / W);
-        std::vector<u32> init_idx;
-        for (int i = 0; i < k; ++i) init_idx.push_back(add(&inits[(size_t)i * W]));
-        for (size_t q = 0; q < st.size(); ++q) {
-            const std::vector<u64> s = st[q];  // (a copy: add() grows st)
-            for_each_successor(m, s.data(), [&](int, const u64* ns) { add(ns); });
-        }
-        LiveHostStrong res;
-        LiveHost& h = res.h;
-        sr_live_strong& sg = res.s;
-        h.unique = st.size();
-        h.r.ran = sg.ran = 1;
-        auto find = [&](const u64* ns) {
-            auto it = index.find(std::vector<u64>(ns, ns + W));
-            if (it == index.end()) throw Error(SR_ERR_NONDETERMINISM, "liveness: a successor of a reachable state is not in the reachable set");
-            return it->second;
-        };
-        // the progress fixpoint, as live_host<true> runs it
-        std::vector<char> alive(st.size(), 0);
-        {
-            std::vector<u32> wl, next;
-            for (u32 i = 0; i < (u32)st.size(); ++i)
-                if (live_not_p(m, p, st[i].data())) alive[i] = 1, wl.push_back(i);
-            h.r.not_p_states = h.r.surviving = wl.size();
-            auto is_alive = [&](const u64* ns) { return alive[find(ns)] != 0; };
-            u64 out[W];
-            for (;;) {
-                u64 removed = 0;
-                next.clear();
-                h.r.rounds += 1;
-                h.r.examined += wl.size();
-                for (u32 i : wl) {
-                    const int a = live_step<true, MOVES>(m, st[i].data(), is_alive, out);
-                    if (a >= 0) next.push_back(i);
-                    else if (a == LIVE_DEAD) alive[i] = 0, ++removed;
-                }
-                wl.swap(next);
-                h.r.surviving -= removed;
-                if (!removed) break;
-            }
-        }
-        const auto t1 = std::chrono::steady_clock::now();
-        // G': the states of F_p' (numbered by `pos`), their edges to other states of F_p', predecessors
-        std::vector<u32> fs, pos(st.size(), NONE);
-        for (u32 i = 0; i < (u32)st.size(); ++i)
-            if (alive[i]) pos[i] = (u32)fs.size(), fs.push_back(i);
-        const u32 nf = (u32)fs.size();
-        struct Edge {
-            u32 a, t;
-        };
-        std::vector<std::vector<Edge>> out_e(nf);
-        std::vector<std::vector<u32>> preds(nf);
-        std::vector<u64> me((size_t)nf * MW);
-        std::vector<char> sink(nf, 0);
-        for (u32 v = 0; v < nf; ++v) {
-            live_moving<MOVES>(m, st[fs[v]].data(), &me[(size_t)v * MW], [&](int a, const u64* ns) {
-                const u32 t = pos[find(ns)];
-                if (t != NONE) out_e[v].push_back({(u32)a, t}), preds[t].push_back(v);
+LiveHostFair<sr_live_weak> live_host_weak(const M& m, int p, u64 max_states) {
+    return live_host_fair<LiveWeakWalk, sr_live_weak, MOVES>(
+        m, p, max_states, [](auto& G, sr_live_weak& wk, std::vector<u32>& node, std::vector<std::vector<u32>>& members, std::vector<u64>& and_me) {
+            constexpr int MW = M::MW;
+            constexpr u32 NONE = ~0u;
+            std::vector<u32> all(G.nf), comp(G.nf, NONE);
+            for (u32 v = 0; v < G.nf; ++v) all[v] = v;
+            G.components(all, [](u32) { return true; }, [&](std::vector<u32>& c) {
+                for (u32 x : c) comp[x] = (u32)members.size();
+                members.push_back(std::move(c));
             });
-            bool any = false;
-            for (int w = 0; w < MW; ++w) any = any || me[(size_t)v * MW + w];
-            sink[v] = !any;
-        }
-        // |U|: F_p' without its sinks, trimmed to the states with a successor in it
-        {
-            std::vector<char> in_u(nf);
-            std::vector<u32> cnt(nf, 0), todo;
-            for (u32 v = 0; v < nf; ++v) in_u[v] = !sink[v];
-            for (u32 v = 0; v < nf; ++v) {
-                for (const Edge& e : out_e[v]) cnt[v] += in_u[e.t];
-                if (in_u[v] && !cnt[v]) todo.push_back(v);
+            wk.components = members.size();
+            and_me.assign(members.size() * MW, ~0ull);
+            std::vector<u64> or_took(members.size() * MW, 0);
+            for (u32 v = 0; v < G.nf; ++v) {
+                if (comp[v] == NONE) continue;
+                for (int w = 0; w < MW; ++w) and_me[(size_t)comp[v] * MW + w] &= G.me[(size_t)v * MW + w];
+                for (const auto& e : G.out_e[v])
+                    if (comp[e.t] == comp[v]) or_took[(size_t)comp[v] * MW + (e.a >> 6)] |= 1ull << (e.a & 63);
             }
-            while (!todo.empty()) {
-                const u32 v = todo.back();
-                todo.pop_back();
-                in_u[v] = 0;
-                for (u32 q : preds[v])
-                    if (in_u[q] && --cnt[q] == 0) todo.push_back(q);
+            std::vector<char> fair(members.size(), 0);
+            for (size_t c = 0; c < members.size(); ++c) {
+                fair[c] = live_fair_masks<MW>(&and_me[c * MW], &or_took[c * MW]);
+                wk.fair_components += fair[c];
             }
-            for (u32 v = 0; v < nf; ++v) sg.cyclic_states += in_u[v];
-        }
-        // The decomposition tree. A job is a vertex set X and its depth; in_x[v] == the job's number while
-        // it runs. Tarjan (iterative) yields the components of G'[X]; a fair node keeps its number in node[v]
-        // and its or_me mask, an unfair one puts X' on the stack.
-        std::vector<u32> node(nf, NONE);
-        std::vector<std::vector<u32>> members;  // per fair node
-        std::vector<u64> node_or_me;            // per fair node, MW words
-        {
+            for (u32 v = 0; v < G.nf; ++v)
+                if (comp[v] != NONE && fair[comp[v]]) node[v] = comp[v];
+        });
+}
+
+// STRONG FAIRNESS on the host: the decomposition tree component by component. A job is a vertex set X and its
+// depth; in_x[v] == the job's number while it runs. Tarjan yields the components of G'[X]; a fair node keeps
+// its number in node[v] and its or_me mask, an unfair one puts X' on the stack.
+template <bool MOVES = true, class M>
+LiveHostFair<sr_live_strong> live_host_strong(const M& m, int p, u64 max_states) {
+    return live_host_fair<LiveStrongWalk, sr_live_strong, MOVES>(
+        m, p, max_states, [](auto& G, sr_live_strong& sg, std::vector<u32>& node, std::vector<std::vector<u32>>& members, std::vector<u64>& node_or_me) {
+            constexpr int MW = M::MW;
+            constexpr u32 NONE = ~0u;
             struct Job {
                 std::vector<u32> x;
                 u32 depth;
             };
-            std::vector<Job> jobs;
-            {
-                Job all{{}, 1};
-                for (u32 v = 0; v < nf; ++v) all.x.push_back(v);
-                jobs.push_back(std::move(all));
-            }
-            std::vector<u32> in_x(nf, NONE), in_c(nf, NONE), num(nf), low(nf), at(nf), stack, call;
-            std::vector<char> on(nf, 0);
+            std::vector<Job> jobs(1, Job{{}, 1});
+            for (u32 v = 0; v < G.nf; ++v) jobs[0].x.push_back(v);
+            std::vector<u32> in_x(G.nf, NONE), in_c(G.nf, NONE);
             u32 job_no = 0, comp_no = 0;
             while (!jobs.empty()) {
                 const Job job = std::move(jobs.back());
                 jobs.pop_back();
                 const u32 tag = job_no++;
-                for (u32 v : job.x) in_x[v] = tag, num[v] = NONE, at[v] = 0;
-                u32 counter = 0;
-                for (u32 root : job.x) {
-                    if (num[root] != NONE) continue;
-                    call.push_back(root);
-                    while (!call.empty()) {
-                        const u32 v = call.back();
-                        if (num[v] == NONE) num[v] = low[v] = counter++, stack.push_back(v), on[v] = 1;
-                        bool down = false;
-                        while (at[v] < out_e[v].size()) {
-                            const u32 t = out_e[v][at[v]].t;
-                            if (in_x[t] == tag) {
-                                if (num[t] == NONE) {
-                                    call.push_back(t);
-                                    down = true;
-                                    break;
-                                }
-                                if (on[t]) low[v] = std::min(low[v], num[t]);
-                            }
-                            ++at[v];
-                        }
-                        if (down) continue;
-                        call.pop_back();
-                        if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[v]);
-                        if (low[v] != num[v]) continue;
-                        std::vector<u32> c;
-                        for (;;) {
-                            const u32 x = stack.back();
-                            stack.pop_back();
-                            on[x] = 0;
-                            c.push_back(x);
-                            if (x == v) break;
-                        }
-                        if (c.size() < 2) continue;
-                        sg.components += 1;
-                        sg.levels = std::max(sg.levels, job.depth);
-                        const u32 cn = comp_no++;
-                        for (u32 x : c) in_c[x] = cn;
-                        u64 or_me[MW] = {}, or_took[MW] = {};
-                        for (u32 x : c) {
-                            for (int w = 0; w < MW; ++w) or_me[w] |= me[(size_t)x * MW + w];
-                            for (const Edge& e : out_e[x])
-                                if (in_c[e.t] == cn) or_took[e.a >> 6] |= 1ull << (e.a & 63);
-                        }
-                        if (live_strong_masks<MW>(or_me, or_took)) {
-                            for (u32 x : c) node[x] = (u32)members.size();
-                            members.push_back(std::move(c));
-                            node_or_me.insert(node_or_me.end(), or_me, or_me + MW);
-                            sg.fair_components += 1;
-                            continue;
-                        }
-                        Job sub{{}, job.depth + 1};
-                        for (u32 x : c) {
-                            bool hit = false;
-                            for (int w = 0; w < MW; ++w) hit = hit || (me[(size_t)x * MW + w] & or_me[w] & ~or_took[w]);
-                            if (!hit) sub.x.push_back(x);
-                        }
-                        if (sub.x.size() >= c.size()) throw Error(SR_ERR_NONDETERMINISM, "liveness: an unfair component loses no state");
-                        if (sub.x.size() >= 2) jobs.push_back(std::move(sub));
+                for (u32 v : job.x) in_x[v] = tag;
+                G.components(job.x, [&](u32 t) { return in_x[t] == tag; }, [&](std::vector<u32>& c) {
+                    sg.components += 1;
+                    sg.levels = std::max(sg.levels, job.depth);
+                    const u32 cn = comp_no++;
+                    for (u32 x : c) in_c[x] = cn;
+                    u64 or_me[MW] = {}, or_took[MW] = {};
+                    for (u32 x : c) {
+                        for (int w = 0; w < MW; ++w) or_me[w] |= G.me[(size_t)x * MW + w];
+                        for (const auto& e : G.out_e[x])
+                            if (in_c[e.t] == cn) or_took[e.a >> 6] |= 1ull << (e.a & 63);
                     }
-                }
+                    if (live_strong_masks<MW>(or_me, or_took)) {
+                        for (u32 x : c) node[x] = (u32)members.size();
+                        members.push_back(std::move(c));
+                        node_or_me.insert(node_or_me.end(), or_me, or_me + MW);
+                        sg.fair_components += 1;
+                        return;
+                    }
+                    Job sub{{}, job.depth + 1};
+                    for (u32 x : c) {
+                        bool hit = false;
+                        for (int w = 0; w < MW; ++w) hit = hit || (G.me[(size_t)x * MW + w] & or_me[w] & ~or_took[w]);
+                        if (!hit) sub.x.push_back(x);
+                    }
+                    if (sub.x.size() >= c.size()) throw Error(SR_ERR_NONDETERMINISM, "liveness: an unfair component loses no state");
+                    if (sub.x.size() >= 2) jobs.push_back(std::move(sub));
+                });
             }
-        }
-        // breadth-first ranks towards `targets` over the predecessors inside a domain (dom(v))
-        auto ranks_to = [&](const std::vector<u32>& targets, auto&& dom, std::vector<u32>& rank) -> u32 {
-            std::vector<u32> level = targets, nxt;
-            for (u32 v : targets) rank[v] = 0;
-            u32 rounds = 0;
-            for (u32 r = 1; !level.empty(); ++r, ++rounds) {
-                nxt.clear();
-                for (u32 t : level)
-                    for (u32 q : preds[t])
-                        if (dom(q) && rank[q] == NONE) rank[q] = r, nxt.push_back(q);
-                level.swap(nxt);
-            }
-            return rounds;
-        };
-        std::vector<u32> rank(nf, NONE), goal;
-        for (u32 v = 0; v < nf; ++v)
-            if (sink[v] || node[v] != NONE) goal.push_back(v);
-        sg.goal_states = goal.size();
-        sg.reach_rounds += ranks_to(goal, [](u32) { return true; }, rank);
-        for (u32 v = 0; v < nf; ++v) sg.fair_states += rank[v] != NONE;
-        for (int i = 0; i < k && h.r.init_index < 0; ++i)
-            if (alive[init_idx[i]] && rank[pos[init_idx[i]]] != NONE) h.r.init_index = i;
-        if (h.r.init_index >= 0) {
-            u64 taken[MW] = {};
-            u32 cur = pos[init_idx[h.r.init_index]];
-            h.words.assign(st[fs[cur]].begin(), st[fs[cur]].end());
-            // follows the lowest rank-lowering slot from cur to rank 0, then takes slot `then` (if >= 0)
-            auto walk = [&](const std::vector<u32>& rk, int then, bool loop) {
-                u64 mk[MW], nx[W];
-                auto step_to = [&](int a) {
-                    h.actions.push_back(m.action_id(st[fs[cur]].data(), a));
-                    if (loop) taken[a >> 6] |= 1ull << (a & 63);
-                    cur = pos[find(nx)];
-                    if (cur == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness leaves F_p'");
-                    h.words.insert(h.words.end(), nx, nx + W);
-                };
-                for (;;) {
-                    const u32 r = rk[cur];
-                    if (r == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is at a state without a rank");
-                    if (!r) break;
-                    const int a = live_descend_step<MOVES>(
-                        m, st[fs[cur]].data(), r,
-                        [&](const u64* ns) {
-                            const u32 t = pos[find(ns)];
-                            return t == NONE ? NONE : rk[t];
-                        },
-                        mk, nx);
-                    if (a < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a ranked state has no successor of a lower rank");
-                    step_to(a);
-                }
-                if (then >= 0) {
-                    if (!m.apply(st[fs[cur]].data(), then, nx)) throw Error(SR_ERR_NONDETERMINISM, "liveness: the slot to take is refused");
-                    step_to(then);
-                }
-            };
-            walk(rank, -1, false);
-            sg.stem_len = (int64_t)h.actions.size();
-            const u32 g = cur;
-            if (sink[g]) {
-                u64 all = 0;
-                for_each_successor(m, st[fs[g]].data(), [&](int, const u64*) { ++all; });
-                h.r.end_kind = all ? SR_LIVE_END_STUTTER : SR_LIVE_END_TERMINAL;
-                sg.loop_len = 0;
-            } else {
-                const u32 c = node[g];
-                if (c == NONE) throw Error(SR_ERR_NONDETERMINISM, "liveness: the stem ends outside every fair node");
-                std::vector<u32> lrank(nf, NONE), targets;
-                auto in_c = [&](u32 v) { return node[v] == c; };
-                auto segment = [&](int then) {
-                    for (u32 v : members[c]) lrank[v] = NONE;
-                    sg.reach_rounds += ranks_to(targets, in_c, lrank);
-                    sg.segments += 1;
-                    walk(lrank, then, true);
-                };
-                for (int a = 0; a < m.max_actions(); ++a) {
-                    if (live_strong_plan(a, taken, &node_or_me[(size_t)c * MW]) == LIVE_PLAN_SKIP) continue;
-                    targets.clear();
-                    for (u32 v : members[c])
-                        for (const Edge& e : out_e[v])
-                            if ((int)e.a == a && node[e.t] == c) {
-                                targets.push_back(v);
-                                break;
-                            }
-                    segment(a);
-                }
-                targets.assign(1, g);
-                segment(-1);
-                h.r.end_kind = SR_LIVE_END_LOOP;
-                h.r.loop_start = sg.stem_len;
-                sg.loop_len = (int64_t)h.actions.size() - sg.stem_len;
-                if (!live_loop_strong_fair(m, &h.words[(size_t)sg.stem_len * W], (size_t)sg.loop_len))
-                    throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness is not strongly fair");
-            }
-            h.r.witness_len = (int64_t)h.actions.size();
-        }
-        const auto t2 = std::chrono::steady_clock::now();
-        h.r.pass_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
-        sg.pass_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-        return res;
-    }
+        });
 }
 
 }  // namespace sr
