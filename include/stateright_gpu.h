@@ -177,7 +177,10 @@ typedef struct sr_opts {
                                     and then nothing changes. The struct grew from 56 to 64 bytes for it: a
                                     caller whose struct_size is 56 is read as liveness = 0, whatever its
                                     padding holds                                                   */
-    int32_t reserved1;
+    int32_t coverage;            /* 1 = the coverage pass behind a check that explored everything (see
+                                    sr_gpu_bfs_coverage below); 0 = off, and then nothing changes. What was
+                                    `reserved1`: the size and every offset are unchanged, and a caller
+                                    whose struct_size is 56 is read as coverage = 0                  */
 } sr_opts;
 
 /* Timing/throughput counters of a finished run (sr_gpu_bfs_stats / sr_gpu_bfs_stats_sized).
@@ -484,6 +487,57 @@ int64_t sr_liveness_host_strong(int32_t model_id, const int64_t* params, int32_t
  * fairness classes. */
 int32_t sr_gpu_bfs_loop_strongly_fair(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n,
                                       int32_t loop_start);
+/* ---- The coverage pass (sr_opts.coverage = 1, off by default; stateright_amd/csrc/cover.hpp has the
+ * definition, for host and device from one source) ----
+ * "No discovery over N states" is only worth something if the model did what its author believes: an
+ * action that is never enabled, or is enabled but always cut by the boundary, makes every `always`
+ * property hold vacuously, and so does a property whose condition holds nowhere or everywhere. With
+ * coverage = 1 a one-GPU search that ended having explored everything is followed by one more expansion
+ * of every reachable state, on the GPU and without the visited set, that counts: per ACTION CLASS c
+ * (the class of slot a at state s is a itself, or what the model's optional `cover_class` hook says:
+ * include/stateright_gpu_model.hpp) enabled[c] (slots of enabled(s)), taken[c] (those for which apply
+ * yields a state within the boundary) and moved[c] (those whose state differs from s); per state, with
+ * deg its taken and mdeg its moved slots, terminal (deg = 0), stutter_ends (deg > 0, mdeg = 0),
+ * out_degree[min(deg, 63)] and max_out_degree; per property, the states where its CONDITION holds. Every
+ * distinct reachable state counts once (a repeated init state too). The search itself is unchanged: the
+ * pass reads the arena behind it, and with the option off no kernel, count or allocation differs.
+ * ran = 0: the option is off or the search did not explore everything (it stopped with every property
+ * discovered). Refused at spawn with SR_ERR_UNSUPPORTED: the partitioned spawns, symmetry (the counts
+ * would be over orbit representatives), target_state_count, a model of more than 1024 classes. Plugin
+ * models take it; the simulation checker ignores it. What the figures do not say: which action FOUND a
+ * state first (that depends on the visit order), anything per depth, anything about simulation traces. */
+typedef struct sr_coverage {
+    uint32_t struct_size;     /* sizeof this struct in the caller's build (set before the call)          */
+    int32_t ran;              /* 1 = the pass ran; with 0 every field below is 0                          */
+    uint64_t states;          /* |R|: equals unique_state_count                                           */
+    uint64_t terminal;        /* states without a taken slot                                              */
+    uint64_t stutter_ends;    /* states with taken slots, every one of them the state itself              */
+    uint32_t max_out_degree;  /* the most taken slots of one state (not clamped)                          */
+    int32_t classes;          /* action classes, at most 1024                                             */
+    int32_t nprops;           /* properties                                                               */
+    int32_t reserved0;
+    double pass_ms;           /* wall time of the pass                                                    */
+    uint64_t out_degree[64];  /* states by taken slots; the last bucket holds 63 and more                 */
+} sr_coverage;
+/* Fills *out (at most out->struct_size bytes) for a joined check. SR_ERR_ARG for a handle that still runs. */
+int32_t sr_gpu_bfs_coverage(const sr_bfs* bfs, sr_coverage* out);
+/* The per-class counts (each array may be NULL; at most cap entries are written). Returns the number of
+ * classes, 0 if the pass did not run. */
+int32_t sr_gpu_bfs_coverage_classes(const sr_bfs* bfs, uint64_t* enabled, uint64_t* taken, uint64_t* moved, int32_t cap);
+/* Per property, the states where its condition holds. Returns the number of properties, 0 if the pass did
+ * not run. */
+int32_t sr_gpu_bfs_coverage_props(const sr_bfs* bfs, uint64_t* holds, int32_t cap);
+/* Copies the name of class c (NUL-terminated); returns its length, or SR_ERR_ARG. */
+int32_t sr_gpu_bfs_coverage_class_name(const sr_bfs* bfs, int32_t c, char* name, int32_t cap);
+/* Host-only (no device needed): the same figures by a host search of a registered model over at most
+ * max_states states (SR_ERR_CAPACITY beyond) and the same per-state rule. enabled, taken, moved take at most
+ * class_cap entries and holds at most prop_cap (each may be NULL); names (may be NULL) receives the class
+ * names, each followed by a newline, cut at names_cap - 1 bytes and NUL-terminated. Returns the model's
+ * unique state count, or a negative SR_ERR_*. */
+int64_t sr_coverage_host(int32_t model_id, const int64_t* params, int32_t nparams, int64_t max_states, sr_coverage* out,
+                         uint64_t* enabled, uint64_t* taken, uint64_t* moved, int32_t class_cap, uint64_t* holds,
+                         int32_t prop_cap, char* names, int32_t names_cap);
+
 /* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
  * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds
  * them. The dump is int64s: [states, init states, properties, the init states' numbers..., then per

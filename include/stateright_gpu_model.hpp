@@ -37,6 +37,16 @@
  *                                             at most 64 slots; SR_ACTION_TABLE=0 keeps apply)
  *             SR_HD canonical(s, out)         a canonical representative under the model's symmetry
  *                                             (the opt-in symmetry_canonical reduction)
+ *             SR_HD int cover_class(s, a)     the ACTION CLASS of slot a at state s, for the coverage pass
+ *                                             (sr_opts.coverage): 0 <= class < cover_classes(), asked for
+ *                                             the slots of enabled(s) only; with it come the host members
+ *                                             int cover_classes() (at most 1024) and
+ *                                             std::string cover_class_name(int c). Without the three, the
+ *                                             class of a slot is the slot, named action_name(a) if the
+ *                                             model's action ids are its slots (action_id_bound() ==
+ *                                             max_actions()), "slot <a>" otherwise. For a model whose slots
+ *                                             are positions (of a network, of a thread) rather than actions
+ *                                             (Increment: the canonical action id; paxos: the message kind)
  *             SR_HD bool faulted(s)           s lost information when it was built (a state its
  *                                             encoding cannot hold): the check ends with
  *                                             SR_ERR_UNSUPPORTED; model_name() (host) names the

@@ -49,7 +49,7 @@ class sr_opts(ctypes.Structure):
         ("symmetry", ctypes.c_int32),
         ("reserved0", ctypes.c_int32),
         ("liveness", ctypes.c_int32),  # (the struct grew from 56 to 64 bytes for it)
-        ("reserved1", ctypes.c_int32),
+        ("coverage", ctypes.c_int32),  # (what was reserved1: same offset)
     ]
 
 
@@ -108,6 +108,27 @@ class sr_live_weak(_LiveFairStats):
 
 class sr_live_strong(_LiveFairStats):
     _fields_ = _live_fair_fields(("levels", ctypes.c_uint32))
+
+
+class sr_coverage(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("ran", ctypes.c_int32),
+        ("states", ctypes.c_uint64),
+        ("terminal", ctypes.c_uint64),
+        ("stutter_ends", ctypes.c_uint64),
+        ("max_out_degree", ctypes.c_uint32),
+        ("classes", ctypes.c_int32),
+        ("nprops", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("pass_ms", ctypes.c_double),
+        ("out_degree", ctypes.c_uint64 * 64),
+    ]
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0", "out_degree")}
+        out["out_degree"] = list(self.out_degree)
+        return out
 
 
 class sr_sim_opts(ctypes.Structure):
@@ -290,6 +311,15 @@ SIGNATURES = [
     ("sr_liveness_host_strong", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                  ctypes.POINTER(sr_live_result), ctypes.POINTER(sr_live_strong), _I64P, ctypes.c_int32]),
     ("sr_gpu_bfs_loop_strongly_fair", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32]),
+    ("sr_gpu_bfs_coverage", ctypes.c_int32, [_P, ctypes.POINTER(sr_coverage)]),
+    ("sr_gpu_bfs_coverage_classes", ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                     ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    ("sr_gpu_bfs_coverage_props", ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    ("sr_gpu_bfs_coverage_class_name", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
+    ("sr_coverage_host", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(sr_coverage),
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
     ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
     ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -485,6 +515,42 @@ def host_graph(model_id, params, max_states=1 << 22):
         succ.append(list(zip(d[at + 2:at + 2 + 2 * c:2], d[at + 3:at + 3 + 2 * c:2])))
         at += 2 + 2 * c
     return succ, inits, conds
+
+
+COVER_MAX_CLASSES = 1024
+
+
+def coverage_dict(res, names, enabled, taken, moved, prop_names, holds):
+    """The dict both `coverage_host` and `GpuBfsChecker.coverage` return: the scalars of sr_coverage (ran,
+    states, terminal, stutter_ends, max_out_degree, pass_ms and the counts `n_classes`, `nprops`), `classes`
+    (a list of {name, enabled, taken, moved} in class order), `properties` ({name: holds}) and `out_degree`
+    (64 buckets; the last holds 63 and more)."""
+    out = res.as_dict()
+    out["n_classes"] = out.pop("classes")
+    out["classes"] = [{"name": n, "enabled": e, "taken": t, "moved": m} for n, e, t, m in zip(names, enabled, taken, moved)]
+    out["properties"] = dict(zip(prop_names, holds))
+    return out
+
+
+def coverage_host(model_id, params, max_states=1 << 22, prop_names=None):
+    """The coverage pass of a registered model on the host (sr_coverage_host, csrc/cover.hpp; no device
+    needed): a host search over at most `max_states` states and the per-state rule the GPU pass applies.
+    The dict of `coverage_dict`; the properties are keyed by `prop_names`, or by index without them."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    res = sr_coverage()
+    res.struct_size = ctypes.sizeof(res)
+    en, tk, mv = ((ctypes.c_uint64 * COVER_MAX_CLASSES)() for _ in range(3))
+    holds = (ctypes.c_uint64 * 32)()
+    names = ctypes.create_string_buffer(COVER_MAX_CLASSES * 256)
+    n = lib.sr_coverage_host(model_id, arr, len(params), max_states, ctypes.byref(res), en, tk, mv, COVER_MAX_CLASSES, holds, 32,
+                             names, len(names))
+    if n < 0:
+        raise ValueError(f"sr_coverage_host: {last_error()} (status {n})")
+    c = res.classes
+    keys = list(prop_names) if prop_names is not None else list(range(res.nprops))
+    return coverage_dict(res, names.value.decode().split("\n")[:c], en[:c], tk[:c], mv[:c], keys, holds[:res.nprops])
 
 
 def _liveness_host(name, call, stats=None):

@@ -255,6 +255,19 @@ class CheckerBuilder:
         self._opts.liveness = N.SR_LIVENESS_STRONG if on else 0
         return self
 
+    def coverage(self, on=True):
+        """Engine opt-in: the coverage pass. A `spawn_bfs` / `spawn_dfs` on one GPU
+        that explored everything is followed by one more expansion of every reachable state on the GPU,
+        which counts per action class how often it was enabled, taken (its next state exists and is
+        within the boundary) and moved (that state differs), per property the states where its condition
+        holds, and the terminal states, stutter ends and out-degrees: `GpuBfsChecker.coverage()`,
+        `coverage_report()`, `assert_covered()`. An action that is never taken, or a condition that holds
+        nowhere or everywhere, is how an `always` property comes to hold vacuously. The search itself is
+        unchanged. `target_state_count`, partitions / comm and `symmetry_canonical` are refused at spawn;
+        plugin models take it; `spawn_simulation` ignores it. Off by default; with it off nothing changes."""
+        self._opts.coverage = int(bool(on))
+        return self
+
     def verbose(self, on=True):
         self._opts.verbose = int(bool(on))
         return self
@@ -630,6 +643,59 @@ class GpuBfsChecker:
                 if s.ran:
                     out[mode] = s.as_dict()
         return out
+
+    def coverage(self):
+        """The coverage pass' figures (`CheckerBuilder.coverage()`; joins the check), a dict: states (the
+        distinct reachable states: `unique_state_count()`), terminal (states where no action yields a
+        state), stutter_ends (states whose every successor is the state itself), max_out_degree, out_degree
+        (states by number of successors, 64 buckets, the last for 63 and more), pass_ms, n_classes, nprops,
+        `classes`: a list of {name, enabled, taken, moved} per action class (enabled: listed by `actions`;
+        taken: with a next state within the boundary; moved: with one that differs from the state), and
+        `properties`: {name: states where the property's condition holds}. Raises CheckerError if the
+        option was off or the search did not explore everything (it stopped with every property
+        discovered)."""
+        self.join()
+        res = N.sr_coverage()
+        res.struct_size = ctypes.sizeof(res)
+        st = self._lib.sr_gpu_bfs_coverage(self._h, ctypes.byref(res))
+        if st != 0 or not res.ran:
+            raise CheckerError("sr_gpu_bfs_coverage", st if st != 0 else None)
+        c = res.classes
+        en, tk, mv = ((ctypes.c_uint64 * max(1, c))() for _ in range(3))
+        self._lib.sr_gpu_bfs_coverage_classes(self._h, en, tk, mv, c)
+        holds = (ctypes.c_uint64 * max(1, res.nprops))()
+        self._lib.sr_gpu_bfs_coverage_props(self._h, holds, res.nprops)
+        names = []
+        buf = ctypes.create_string_buffer(256)
+        for i in range(c):
+            self._lib.sr_gpu_bfs_coverage_class_name(self._h, i, buf, 256)
+            names.append(buf.value.decode())
+        return N.coverage_dict(res, names, en[:c], tk[:c], mv[:c], [n for n, _ in self.properties()], holds[:res.nprops])
+
+    def coverage_report(self, w=None):
+        """Prints the coverage table: one line per action class, then the properties and the state figures."""
+        w = w or sys.stdout
+        cov = self.coverage()
+        width = max([len("action class")] + [len(c["name"]) for c in cov["classes"]])
+        w.write(f"Coverage. states={cov['states']}, terminal={cov['terminal']}, stutter_ends={cov['stutter_ends']}, "
+                f"max_out_degree={cov['max_out_degree']}\n")
+        w.write(f"{'action class':<{width}}  {'enabled':>14}  {'taken':>14}  {'moved':>14}\n")
+        for c in cov["classes"]:
+            mark = "" if c["taken"] else "  <- never taken"
+            w.write(f"{c['name']:<{width}}  {c['enabled']:>14}  {c['taken']:>14}  {c['moved']:>14}{mark}\n")
+        for (name, exp), holds in zip(self.properties(), cov["properties"].values()):
+            mark = "  <- holds nowhere" if holds == 0 else "  <- holds everywhere" if holds == cov["states"] else ""
+            w.write(f'{exp.name.lower()} "{name}": condition holds at {holds} of {cov["states"]} states{mark}\n')
+        return self
+
+    def assert_covered(self, allow=()):
+        """Raises AssertionError naming every action class that was never taken (`taken == 0`) and is not
+        in `allow` (class names)."""
+        allow = set(allow)
+        missing = [c["name"] for c in self.coverage()["classes"] if c["taken"] == 0 and c["name"] not in allow]
+        if missing:
+            raise AssertionError(f"action classes never taken: {missing}")
+        return self
 
     def loop_start(self, name):
         """`complete_liveness()`: if the discovery of the `eventually` property `name` is a lasso found

@@ -249,6 +249,22 @@ struct ActorGpu : Sys {
                                 this->format_msg(msg);
         return kind == 1 ? "Deliver { " + env + " }" : "Drop(Envelope { " + env + " })";
     }
+    // Coverage classes (cover.hpp): (Drop | Deliver | Timeout) x destination actor, kind-major: class
+    // kind * nact() + dst; the last class takes what names no actor (the Drop of an
+    // envelope to an id beyond the actors).
+    SR_HD int cover_class(const u64* s, int a) const {
+        const int n = (int)this->nact();
+        if (a >= 2 * K) return a - 2 * K < n ? 2 * n + (a - 2 * K) : 3 * n;
+        const int dst = (int)e_dst(slot(s, a >> 1));
+        return dst < n ? (a & 1) * n + dst : 3 * n;
+    }
+    int cover_classes() const { return 3 * (int)this->nact() + 1; }
+    std::string cover_class_name(int c) const {
+        const int n = (int)this->nact();
+        if (c >= 3 * n) return "Drop(dst: no actor)";
+        const std::string id = "Id(" + std::to_string(c % n) + ")";
+        return c < n ? "Drop(dst: " + id + ")" : c < 2 * n ? "Deliver(dst: " + id + ")" : "Timeout(" + id + ")";
+    }
 };
 
 // ---------------------------------------------------------------------------------------------

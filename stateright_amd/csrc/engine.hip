@@ -58,8 +58,19 @@ static void refuse_liveness(const sr_opts& o, bool partitioned, bool plugin) {
     if (o.symmetry) throw Error(SR_ERR_UNSUPPORTED, "liveness with symmetry: the fixpoint runs on concrete states, not on orbit representatives");
 }
 
+// The coverage pass (sr_opts.coverage, cover.hpp) runs on one GPU's arena, over states (Engine<M> refuses
+// target_state_count and, for a plugin's canonical form too, symmetry).
+static void refuse_coverage(const sr_opts& o, bool partitioned) {
+    if (!o.coverage) return;
+    if (partitioned) throw Error(SR_ERR_UNSUPPORTED, "coverage with a partitioned search: the pass counts over one GPU's arena");
+    if (o.symmetry) throw Error(SR_ERR_UNSUPPORTED, "coverage with symmetry: the counts would be over orbit representatives, not over states");
+    if (o.target_state_count)
+        throw Error(SR_ERR_UNSUPPORTED, "coverage with target_state_count: the counts are over the whole reachable set");
+}
+
 static std::unique_ptr<EngineBase> make_engine(int model, const i64* p, int np, const sr_opts& o) {
     refuse_liveness(o, false, false);
+    refuse_coverage(o, false);
     return make_model_engine(EngineArgs{model, p, np, &o, false, nullptr, 0});
 }
 
@@ -341,6 +352,7 @@ static sr_bfs* spawn_plugin(const sr_plugin* pl, sr_dist* comm, int32_t vparts, 
                                         std::to_string(pl->abi) + ", engine " + std::to_string(SR_PLUGIN_ABI) + ")");
         sr_opts o = normalized_opts(opts);
         refuse_liveness(o, comm != nullptr || vparts > 1, true);
+        refuse_coverage(o, comm != nullptr || vparts > 1);
         if (comm) o.device = comm->c->device;
         if (sr_device_count() <= 0) throw Error(SR_ERR_NO_DEVICE, "no HIP device visible");
         char err[512] = {0};
@@ -784,6 +796,83 @@ int64_t sr_liveness_host_strong(int32_t model, const int64_t* p, int32_t np, int
     return liveness_host_entry("sr_liveness_host_strong", args, "strong fairness", model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) {
         return live_host_split(moves ? live_host_strong<true>(m, prop, (u64)max_states) : live_host_strong<false>(m, prop, (u64)max_states), strong);
     });
+}
+
+// Copies the fixed part of a pass' figures into the caller's mirror (at most its struct_size bytes).
+static void cover_copy_out(const sr_coverage& c, sr_coverage* out) {
+    sr_coverage r = c;
+    r.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(r));
+    std::memcpy(out, &r, r.struct_size);  // only the caller's own bytes
+}
+
+int32_t sr_gpu_bfs_coverage(const sr_bfs* b, sr_coverage* out) {
+    if (!b || !out || out->struct_size < 2 * sizeof(uint32_t) || !b->e->finished.load(std::memory_order_acquire)) {
+        set_error("sr_gpu_bfs_coverage: a finished check and a sized result struct");
+        return SR_ERR_ARG;
+    }
+    cover_copy_out(b->e->cover.c, out);
+    if (!b->e->cover.c.ran) set_error("coverage: the pass did not run (the option is off, or the search did not explore everything)");
+    return SR_OK;
+}
+
+int32_t sr_gpu_bfs_coverage_classes(const sr_bfs* b, uint64_t* enabled, uint64_t* taken, uint64_t* moved, int32_t cap) {
+    if (!b || !b->e->finished.load(std::memory_order_acquire)) return SR_ERR_ARG;
+    const CoverFigures& f = b->e->cover;
+    if (!f.c.ran) return 0;
+    for (int32_t c = 0; c < cap && c < f.c.classes; ++c) {
+        if (enabled) enabled[c] = f.enabled[(size_t)c];
+        if (taken) taken[c] = f.taken[(size_t)c];
+        if (moved) moved[c] = f.moved[(size_t)c];
+    }
+    return f.c.classes;
+}
+
+int32_t sr_gpu_bfs_coverage_props(const sr_bfs* b, uint64_t* holds, int32_t cap) {
+    if (!b || !b->e->finished.load(std::memory_order_acquire)) return SR_ERR_ARG;
+    const CoverFigures& f = b->e->cover;
+    if (!f.c.ran) return 0;
+    for (int32_t p = 0; holds && p < cap && p < f.c.nprops; ++p) holds[p] = f.holds[(size_t)p];
+    return f.c.nprops;
+}
+
+int32_t sr_gpu_bfs_coverage_class_name(const sr_bfs* b, int32_t c, char* name, int32_t cap) {
+    if (!b || !b->e->finished.load(std::memory_order_acquire) || c < 0 || c >= (int32_t)b->e->cover.names.size()) return SR_ERR_ARG;
+    const std::string& s = b->e->cover.names[(size_t)c];
+    if (name && cap > 0) std::snprintf(name, (size_t)cap, "%s", s.c_str());
+    return (int32_t)s.size();
+}
+
+int64_t sr_coverage_host(int32_t model, const int64_t* p, int32_t np, int64_t max_states, sr_coverage* out, uint64_t* enabled,
+                         uint64_t* taken, uint64_t* moved, int32_t class_cap, uint64_t* holds, int32_t prop_cap, char* names,
+                         int32_t names_cap) {
+    try {
+        if (!out || out->struct_size < 2 * sizeof(uint32_t) || max_states < 1)
+            throw Error(SR_ERR_ARG, "sr_coverage_host: a sized result struct and max_states >= 1");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            const CoverFigures f = cover_host(m, (u64)max_states);
+            cover_copy_out(f.c, out);
+            for (int32_t c = 0; c < class_cap && c < f.c.classes; ++c) {
+                if (enabled) enabled[c] = f.enabled[(size_t)c];
+                if (taken) taken[c] = f.taken[(size_t)c];
+                if (moved) moved[c] = f.moved[(size_t)c];
+            }
+            for (int32_t q = 0; holds && q < prop_cap && q < f.c.nprops; ++q) holds[q] = f.holds[(size_t)q];
+            if (names && names_cap > 0) {
+                std::string all;
+                for (const std::string& s : f.names) all += s + "\n";
+                std::snprintf(names, (size_t)names_cap, "%s", all.c_str());
+            }
+            return (i64)f.c.states;
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_coverage_host: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
 }
 
 int64_t sr_host_graph(int32_t model, const int64_t* p, int32_t np, int64_t max_states, int64_t* out, int64_t cap) {
@@ -1514,6 +1603,7 @@ sr_bfs* sr_gpu_bfs_spawn_partitioned(sr_dist* comm, int32_t virtual_parts, int32
     try {
         sr_opts o = normalized_opts(opts);
         refuse_liveness(o, true, false);
+        refuse_coverage(o, true);
         if (comm) o.device = comm->c->device;
         if (sr_device_count() <= 0) throw Error(SR_ERR_NO_DEVICE, "no HIP device visible");
         return start(make_model_engine(EngineArgs{model_id, params, nparams, &o, true, comm ? comm->c.get() : nullptr, (int)virtual_parts}));

@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "kernels_audit.hpp"
 #include "live.hpp"
+#include "cover.hpp"
 
 namespace sr {
 
@@ -109,6 +110,7 @@ class EngineBase {
     std::vector<sr_live_result> live;  // per property (empty: the pass never ran)
     std::vector<sr_live_weak> live_weak;  // per property (empty: the pass never ran in the weak mode)
     std::vector<sr_live_strong> live_strong;  // per property (empty: the pass never ran in the strong mode)
+    CoverFigures cover;  // the coverage pass' figures (cover.hpp; c.ran = 0: it did not run)
     std::atomic<u64> state_count{0}, unique{0};
     std::atomic<u32> max_depth{0};
     std::atomic<bool> finished{false};
@@ -404,6 +406,15 @@ class Engine final : public EngineBase {
                 throw Error(SR_ERR_UNSUPPORTED, "weak fairness: this model's slots are not fairness classes");
             if (o_.liveness == SR_LIVENESS_STRONG && !(fair_slots_model<M> && M::MW <= LIVE_MW_MAX))
                 throw Error(SR_ERR_UNSUPPORTED, "strong fairness: this model's slots are not fairness classes");
+        }
+        cover.c = cover_none();
+        if (o_.coverage) {  // the coverage pass (cover.hpp): what it cannot be combined with
+            if (o_.target_state_count)
+                throw Error(SR_ERR_UNSUPPORTED, "coverage with target_state_count: the counts are over the whole reachable set");
+            if (is_canon<M>::value)
+                throw Error(SR_ERR_UNSUPPORTED, "coverage with symmetry: the counts would be over orbit representatives, not over states");
+            (void)cover_checked_classes(m_);
+            static_assert(cover_chunk_max<M>() >= 1, "coverage: an LDS counter must hold one stride");
         }
         // Internal tuning knobs (not part of the ABI): successors per lane per probe round and
         // the visited-set load factor the capacity hint is sized for.
@@ -1008,6 +1019,8 @@ class Engine final : public EngineBase {
         live_weak.clear();
         live_strong.clear();
         live_path_.assign(M::NPROPS, {});
+        cover = CoverFigures{};
+        cover.c = cover_none();
         stats = sr_stats{};
         stats.words_per_state = W;
         stats.order_used = (u32)order;
@@ -1097,9 +1110,12 @@ class Engine final : public EngineBase {
         u32 level = 0;
         bool order_dependent = false;
         bool explored_all = false;  // every level was expanded whole and the last one produced nothing
+        bool cover_all = false;     // the same for the pipelined loop (which the liveness pass never follows)
         auto t_loop = Clock::now();
-        if (pipelined) order_dependent = pipeline_levels(n, sq_level0);
-        else for (;;) {
+        if (pipelined) {
+            order_dependent = pipeline_levels(n, sq_level0);
+            cover_all = !order_dependent;  // (it returns true whenever it stopped with every property discovered)
+        } else for (;;) {
             // 1. Discoveries among this level's states (evaluated when they were produced).
             u32 newly = 0, max_rank = 0;
             for (int p = 0; p < M::NPROPS; ++p)
@@ -1233,6 +1249,7 @@ class Engine final : public EngineBase {
         stats.total_sec = secs(t_start, t_end);
         stats.table_capacity = cap_;
         if (o_.liveness && explored_all) live_pass();  // (reads the visited set: before its release)
+        if (o_.coverage && (explored_all || cover_all)) cover_pass();  // (reads the arena only)
         release_table();  // (the pipelined loop released it already)
         free_unzeroed_table();
         return order_dependent && !fifo_;
@@ -1430,6 +1447,76 @@ class Engine final : public EngineBase {
         if (!table_recycle_ || fifo_ || o_.counters || !table_unzeroed_ || !keys_.p) return;
         SR_HIP(stream_sync(stream_));
         keys_.reset();
+    }
+
+    // The coverage pass (cover.hpp, kernels_cover.hpp) behind a search that explored everything: one launch
+    // of cover_count over the arena, the persistent grid sized from the kernel's occupancy, and one read-back
+    // of its 64-bit counters. Level 0 of the arena holds the init states as given, in REVERSE order: the
+    // indices that repeat another init state are handed to the kernel as a bit mask and count nothing. Every
+    // buffer lives for this call only. SR_COVER_GRID and SR_COVER_CHUNK (tests: several strides and several
+    // flushes on a small arena) override the grid and the strides between two flushes.
+    void cover_pass() {
+        const auto t0 = Clock::now();
+        CoverFigures f = cover_figures_for(m_);
+        const u32 C = (u32)f.c.classes;
+        const u64 n = lstart_.back();
+        const std::vector<u64> inits = init_states_of(m_);
+        const u32 k = (u32)(inits.size() / W);
+        std::vector<u32> skip((k + 31) / 32, 0u);
+        u64 dups = 0;
+        {
+            std::set<std::vector<u64>> seen;
+            for (u32 i = 0; i < k; ++i)
+                if (!seen.insert(std::vector<u64>(&inits[(size_t)i * W], &inits[(size_t)i * W] + W)).second) {
+                    const u32 at = k - 1 - i;  // init state i is arena index k - 1 - i
+                    skip[at >> 5] |= 1u << (at & 31);
+                    ++dups;
+                }
+        }
+        DBuf<u64> g;
+        DBuf<u32> skip_d;
+        const size_t words = cover_words(C);
+        g.alloc(o_.device, words);
+        SR_HIP(hipMemsetAsync(g.p, 0, words * sizeof(u64), stream_));
+        if (dups) {
+            skip_d.alloc(o_.device, skip.size());
+            SR_HIP(hipMemcpyAsync(skip_d.p, skip.data(), skip.size() * sizeof(u32), hipMemcpyHostToDevice, stream_));
+        }
+        int per_cu = 0, cus = 0;
+        SR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)cover_count<M>, COVER_BLOCK, 0));
+        SR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o_.device));
+        u64 grid = per_cu > 0 && cus > 0 ? (u64)per_cu * (u64)cus : 1024;
+        u32 chunk = std::min<u32>(cover_chunk_max<M>(), 1024);
+        if (const char* e = std::getenv("SR_COVER_GRID"))
+            if (std::atoi(e) > 0) grid = (u64)std::atoi(e);
+        if (const char* e = std::getenv("SR_COVER_CHUNK"))
+            if (std::atoi(e) > 0) chunk = std::min<u32>((u32)std::atoi(e), cover_chunk_max<M>());
+        grid = std::max<u64>(1, std::min<u64>(grid, (n + COVER_BLOCK - 1) / COVER_BLOCK));
+        cover_count<M><<<(u32)grid, COVER_BLOCK, 0, stream_>>>(m_, arena_.p, n, dups ? skip_d.p : nullptr, dups ? k : 0u, cover_always_mask(m_), C,
+                                                              chunk, g.p);
+        SR_HIP(hipGetLastError());
+        std::vector<u64> h(words);
+        SR_HIP(hipMemcpyAsync(h.data(), g.p, words * sizeof(u64), hipMemcpyDeviceToHost, stream_));
+        SR_HIP(stream_sync(stream_));
+        const u64* tail = &h[(size_t)3 * C];
+        if (tail[COVER_DEGREES + 32 + 3])
+            throw Error(SR_ERR_NONDETERMINISM, "coverage: cover_class named a class outside the model's " + std::to_string(C) + " for " +
+                                                   std::to_string(tail[COVER_DEGREES + 32 + 3]) + " enabled slots");
+        std::copy(&h[0], &h[C], f.enabled.begin());
+        std::copy(&h[C], &h[(size_t)2 * C], f.taken.begin());
+        std::copy(&h[(size_t)2 * C], &h[(size_t)3 * C], f.moved.begin());
+        std::copy(tail, tail + COVER_DEGREES, f.c.out_degree);
+        for (int p = 0; p < M::NPROPS; ++p) f.holds[(size_t)p] = tail[COVER_DEGREES + p];
+        f.c.terminal = tail[COVER_DEGREES + 32];
+        f.c.stutter_ends = tail[COVER_DEGREES + 32 + 1];
+        f.c.max_out_degree = (u32)tail[COVER_DEGREES + 32 + 2];
+        f.c.states = n - dups;
+        f.c.ran = 1;
+        f.c.pass_ms = secs(t0, Clock::now()) * 1e3;
+        if (o_.verbose)
+            std::fprintf(stderr, "[sr] coverage: %llu states, %u classes, grid %llu x %u, %u strides per flush, %.3f ms\n",
+                         (unsigned long long)f.c.states, C, (unsigned long long)grid, COVER_BLOCK, chunk, f.c.pass_ms);
+        cover = std::move(f);
     }
 
     // The complete `eventually` check (live.hpp, kernels_live.hpp) behind a search that explored

@@ -865,6 +865,10 @@ struct Increment {
     std::string action_name(i64 id) const {
         return std::string(id % 2 ? "Write(" : "Read(") + std::to_string(id / 2) + ")";
     }
+    // Coverage classes (cover.hpp): the canonical action ids, Read(t) and Write(t).
+    SR_HD int cover_class(const u64* s, int t) const { return 2 * t + (getb(s, toff(t) + 4, 2) == 2 ? 1 : 0); }
+    int cover_classes() const { return 2 * n; }
+    std::string cover_class_name(int c) const { return action_name(c); }
 };
 
 // -----------------------------------------------------------------------------------------------
@@ -974,6 +978,10 @@ struct IncrementLock {
         const char* names[] = {"Lock", "Read", "Write", "Release"};
         return std::string(names[id % 4]) + "(" + std::to_string(id / 4) + ")";
     }
+    // Coverage classes (cover.hpp): the canonical action ids, Lock / Read / Write / Release(t).
+    SR_HD int cover_class(const u64* s, int t) const { return 4 * t + (int)getb(s, toff(t) + 4, 3); }
+    int cover_classes() const { return 4 * n; }
+    std::string cover_class_name(int c) const { return action_name(c); }
 };
 
 // -----------------------------------------------------------------------------------------------

@@ -897,6 +897,13 @@ struct PaxosT {
         return "Deliver { src: Id(" + std::to_string(src) + "), dst: Id(" + std::to_string(dst) + "), msg: " +
                (kind < 9 ? names[kind] : "?") + " }";
     }
+    // Coverage classes (cover.hpp): the message kind of the envelope in the slot.
+    SR_HD int cover_class(const u64* s, int a) const { return (int)px::e_kind(slot(s, a)); }
+    int cover_classes() const { return 9; }
+    std::string cover_class_name(int c) const {
+        static const char* names[] = {"Prepare", "Prepared", "Accept", "Accepted", "Decided", "Put", "Get", "PutOk", "GetOk"};
+        return c >= 0 && c < 9 ? names[c] : "?";
+    }
 };
 using Paxos = PaxosT<11>;      // up to 4 clients
 using PaxosWide = PaxosT<12>;  // 5 or 6 clients
