@@ -101,7 +101,7 @@ enum sr_model_id {
                                      Two `eventually` properties: 0 "some thread served", 1 "every thread served".
                                      No reference counterpart: the model of the complete `eventually` check's
                                      weak-fairness mode (SR_LIVENESS_WEAK) */
-    SR_MODEL_FAIR_RINGS = 18      /* (d 1..28, w 4..64, core 0..2, lanes 1..512) nested rings; one word: position x
+    SR_MODEL_FAIR_RINGS = 18,     /* (d 1..28, w 4..64, core 0..2, lanes 1..512) nested rings; one word: position x
                                      in bits [0,6), ring k in [6,11), lane j in [11,20), done in bit 20. Lane j has
                                      the rings 0 .. d_j, d_j = 1 + (j mod d); its core is on iff core == 1, or
                                      core == 2 and j is odd. Slot 0 Step (x + 1 mod w); 1 + k Out(k), enabled at
@@ -111,6 +111,22 @@ enum sr_model_id {
                                      (j, 0, 0). No reference counterpart and no oracle counterpart: the fixture of
                                      the complete `eventually` check's strong-fairness mode (SR_LIVENESS_STRONG),
                                      whose fair sets lie d_j levels deep inside unfair components */
+    SR_MODEL_LEADS_GRAPH = 19,    /* (n_bits<=24, degree 1..4, seed, p_mod, t_mod, roots 1..512, q_mod[, words[, dup]])
+                                     SR_MODEL_LIVE_GRAPH's graph, key and description with three properties:
+                                     0 eventually "marked" (as there); 1 leads-to "armed ~> marked", whose trigger
+                                     is q_mod > 0 and r(v, degree + 2) % q_mod == 0; 2 leads-to "always eventually
+                                     marked", whose trigger is true. The fixture of the leads-to check */
+    SR_MODEL_REQ_LOCK = 20,       /* (threads 1..8) a lock whose threads first ask for it, while a clock ticks; one
+                                     word: holder (0 free, i + 1) in bits [0,5), waiting (n bits) from bit 5, tick
+                                     above. Slot i < n Request(i) (i neither waits nor holds: sets waiting(i)), n + i
+                                     Acquire(i) (the lock is free and i waits: i holds, waiting(i) cleared), 2n + i
+                                     Release(i) (i holds: frees the lock), 3n Tick (always: flips tick);
+                                     (2^n + n 2^(n-1)) 2 states. Properties p < n: leads-to "thread p waiting ~>
+                                     thread p holds"; property n: eventually "some thread holds". The model of the
+                                     leads-to check: refuted with no, progress and (n >= 2) weak fairness, proved
+                                     under strong fairness */
+    SR_MODEL_LEADS_DGRAPH = 21    /* (n_trig, t.., len, v.., len, v..) SR_MODEL_DGRAPH's adjacency from paths, with
+                                     an explicit list of trigger nodes; one leads-to property "trigger ~> odd" */
 };
 
 /* Visit order inside a BFS level. */
@@ -136,7 +152,10 @@ enum sr_liveness_mode {
 /* sr_live_result.end_kind: how the witness ends (both modes). */
 enum sr_live_end { SR_LIVE_END_NONE = 0, SR_LIVE_END_TERMINAL = 1, SR_LIVE_END_LOOP = 2, SR_LIVE_END_STUTTER = 3 };
 
-enum sr_expectation { SR_ALWAYS = 0, SR_EVENTUALLY = 1, SR_SOMETIMES = 2 }; /* src/lib.rs:293-300 */
+/* SR_LEADS_TO has no reference counterpart: "whenever the property's trigger holds, its condition holds then
+ * or later" (TLA+'s P ~> Q; always-eventually where the trigger is true). Only the complete liveness check
+ * decides it (see sr_gpu_bfs_liveness_leads below); the search itself never discovers it. */
+enum sr_expectation { SR_ALWAYS = 0, SR_EVENTUALLY = 1, SR_SOMETIMES = 2, SR_LEADS_TO = 3 }; /* src/lib.rs:293-300 */
 
 enum sr_status {
     SR_OK = 0,
@@ -372,8 +391,8 @@ typedef struct sr_live_result {
                                the witness ends at a terminal state                                */
     double pass_ms;         /* wall time of the pass for this property                             */
 } sr_live_result;
-/* The pass' outcome for property `prop` of a joined check (ran = 0: liveness off, not an `eventually`
- * property, discovered by the search itself, or the search did not explore everything). */
+/* The pass' outcome for property `prop` of a joined check (ran = 0: liveness off, neither an `eventually`
+ * nor a leads-to property, discovered by the search itself, or the search did not explore everything). */
 int32_t sr_gpu_bfs_liveness(const sr_bfs* bfs, int32_t prop, sr_live_result* out);
 /* Host-only (no device needed): a host search of a registered model over at most max_states states
  * (SR_ERR_CAPACITY beyond), then the fixpoint and the witness for its `eventually` property `prop`.
@@ -487,6 +506,46 @@ int64_t sr_liveness_host_strong(int32_t model_id, const int64_t* params, int32_t
  * fairness classes. */
 int32_t sr_gpu_bfs_loop_strongly_fair(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n,
                                       int32_t loop_start);
+/* ---- LEADS-TO properties (expectation SR_LEADS_TO; live.hpp and DESIGN.md section 14 have the definition) ----
+ * A leads-to property p has a TRIGGER P and a TARGET condition Q (the property's condition). In every mode of
+ * the complete check, X_Q is the mode's set for Q exactly as for an `eventually` property with that condition:
+ * F_p (no fairness), F_p' (progress) or FairF (weak, strong): the reachable states from which a (fair) maximal
+ * run exists on which Q never holds. p has a counterexample iff some REACHABLE state where P holds is in X_Q.
+ * The seed is the violating state of lowest depth (breadth-first distance from the init states), among those
+ * the lowest compared word by word from word 0, unsigned. The witness is the search's own tree path from an
+ * init state to the seed (its length is the seed's depth; Q may hold on it), followed by the mode's witness
+ * started at the seed. sr_live_result keeps its meanings, over the whole path: witness_len counts all steps,
+ * init_index is the init state the prefix starts at (the lowest index of an equal init state), loop_start is
+ * an index into the whole path and never below trigger_index; sr_live_weak / sr_live_strong stem_len counts
+ * from the seed, so loop_start = trigger_index + stem_len. With liveness off the property is not checked, and
+ * the search stops as if it were absent; with liveness on an undiscovered leads-to property makes the search
+ * explore everything. One seed only; the witness is not the shortest beyond its prefix. */
+typedef struct sr_live_leads {
+    int32_t ran;            /* 1 = the pass ran for this property and it is a leads-to property            */
+    int32_t reserved0;
+    uint64_t triggered;     /* reachable states where the trigger holds                                    */
+    uint64_t pending;       /* ... where the trigger holds and the target condition does not               */
+    uint64_t violating;     /* ... where the trigger holds and that are in X_Q (each state counted once,
+                               whatever number of runs from it avoid Q)                                   */
+    int64_t trigger_index;  /* index of the seed on the witness = length of the prefix; -1 without one     */
+    int64_t trigger_depth;  /* the seed's depth; equals trigger_index; -1 without a witness                */
+    double seed_ms;         /* wall time of the seed stage (counts, seed, tie-break)                       */
+} sr_live_leads;
+/* The leads-to figures for property `prop` of a joined check (ran = 0: not a leads-to property, or
+ * sr_gpu_bfs_liveness would say ran = 0). */
+int32_t sr_gpu_bfs_liveness_leads(const sr_bfs* bfs, int32_t prop, sr_live_leads* out);
+/* Host-only: the trigger of the leads-to property `prop` on every state of the path that the canonical action
+ * ids describe from init state `init` of a joined check's model (what `assert_discovery` asks for a leads-to
+ * property): writes n + 1 entries (0 / 1) and returns n + 1; -1: the actions cannot be replayed, `prop` is no
+ * leads-to property, or cap < n + 1. */
+int32_t sr_gpu_bfs_replay_triggers(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n, int32_t prop,
+                                   int32_t* out, int32_t cap);
+/* Host-only (no device needed): the leads-to check of property `prop` of a registered model in the mode
+ * `fairness` (0 none, 1 progress, 2 weak, 3 strong), built from the host forms above with the seed rule above;
+ * the prefix is the tree path of the reference's FIFO order. Writes the whole witness' canonical action ids
+ * (at most cap). Returns the model's unique state count, or a negative SR_ERR_*. */
+int64_t sr_liveness_host_leads(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int32_t fairness,
+                               int64_t max_states, sr_live_result* out, sr_live_leads* leads, int64_t* action_ids, int32_t cap);
 /* ---- The coverage pass (sr_opts.coverage = 1, off by default; stateright_amd/csrc/cover.hpp has the
  * definition, for host and device from one source) ----
  * "No discovery over N states" is only worth something if the model did what its author believes: an

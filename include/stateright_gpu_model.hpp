@@ -20,6 +20,15 @@
  *                                             its host buffers from it)
  *             undescribe(const i64*, u64*)    (sr_plugin.fingerprint)
  *             emask()                         (the mask of `eventually` properties)
+ *             SR_HD u32 lmask()               the mask of LEADS-TO properties (expectation(p) == LEADS_TO = 3:
+ *                                             "whenever the trigger holds, the condition holds then or later"),
+ *                                             disjoint from emask(); with it comes
+ *                                             SR_HD bool leads_from(int p, const u64* s), the TRIGGER of such a
+ *                                             property, while discovers(p, s) is its condition, as for
+ *                                             `eventually`. Only the complete liveness check decides such a
+ *                                             property, and it refuses plugins, so a plugin's leads-to
+ *                                             properties are left unchecked by every checker (the plugin ABI
+ *                                             version is unchanged); a model without lmask() has none
  *             qkey_bits(), SR_HD qkey(s)      (exact quotient visited set for multi-word states)
  *             SR_HD self_loops(s, enabled, out)   out = enabled slots whose next_state is s itself:
  *                                             FAST expansion counts them (state_count) without

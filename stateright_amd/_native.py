@@ -27,9 +27,12 @@ SR_MODEL_LIVE_GRAPH = 15
 SR_MODEL_2PC_LIVE = 16
 SR_MODEL_SPIN_LOCK = 17
 SR_MODEL_FAIR_RINGS = 18
+SR_MODEL_LEADS_GRAPH = 19
+SR_MODEL_REQ_LOCK = 20
+SR_MODEL_LEADS_DGRAPH = 21
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
-SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES = 0, 1, 2
+SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES, SR_LEADS_TO = 0, 1, 2, 3
 # sr_stats.root_path (enum sr_root_path)
 SR_ROOTS_INLINE, SR_ROOTS_FUSED, SR_ROOTS_LAUNCHES, SR_ROOTS_HEAD, SR_ROOTS_PARTS, SR_ROOTS_BUFFER = 1, 2, 3, 4, 5, 6
 
@@ -108,6 +111,22 @@ class sr_live_weak(_LiveFairStats):
 
 class sr_live_strong(_LiveFairStats):
     _fields_ = _live_fair_fields(("levels", ctypes.c_uint32))
+
+
+class sr_live_leads(ctypes.Structure):
+    _fields_ = [
+        ("ran", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("triggered", ctypes.c_uint64),
+        ("pending", ctypes.c_uint64),
+        ("violating", ctypes.c_uint64),
+        ("trigger_index", ctypes.c_int64),
+        ("trigger_depth", ctypes.c_int64),
+        ("seed_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
 
 
 class sr_coverage(ctypes.Structure):
@@ -310,6 +329,11 @@ SIGNATURES = [
     ("sr_gpu_bfs_liveness_strong", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(sr_live_strong)]),
     ("sr_liveness_host_strong", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                  ctypes.POINTER(sr_live_result), ctypes.POINTER(sr_live_strong), _I64P, ctypes.c_int32]),
+    ("sr_gpu_bfs_liveness_leads", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(sr_live_leads)]),
+    ("sr_gpu_bfs_replay_triggers", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    ("sr_liveness_host_leads", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.POINTER(sr_live_result), ctypes.POINTER(sr_live_leads), _I64P, ctypes.c_int32]),
     ("sr_gpu_bfs_loop_strongly_fair", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32]),
     ("sr_gpu_bfs_coverage", ctypes.c_int32, [_P, ctypes.POINTER(sr_coverage)]),
     ("sr_gpu_bfs_coverage_classes", ctypes.c_int32, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
@@ -613,6 +637,24 @@ def liveness_host_strong(model_id, params, prop=0, max_states=1 << 22):
     witness' `actions` are the stem's followed by the closed walk's; ValueError (status -4) for a model whose
     slots are not fairness classes."""
     return _liveness_host_fair("strong", sr_live_strong(), model_id, params, prop, max_states)
+
+
+LEADS_FAIRNESS = {"none": 0, "progress": 1, "weak": 2, "strong": 3}
+
+
+def liveness_host_leads(model_id, params, prop, fairness=0, max_states=1 << 22):
+    """The leads-to check of a registered model on the host (csrc/live.hpp LEADS-TO; no device needed) for the
+    leads-to property of index `prop` in the mode `fairness` (0 / "none", 1 / "progress", 2 / "weak", 3 /
+    "strong"): the dict of `liveness_host` over the whole witness (`actions`: the prefix' followed by the mode's
+    own), plus `leads`, the dict of sr_live_leads (triggered, pending, violating, trigger_index, trigger_depth,
+    seed_ms)."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    mode = LEADS_FAIRNESS.get(fairness, fairness)
+    stats = sr_live_leads()
+    return _liveness_host("sr_liveness_host_leads", lambda res, acts, cap: lib.sr_liveness_host_leads(
+        model_id, arr, len(params), prop, mode, max_states, res, ctypes.byref(stats), acts, cap), ("leads", stats))
 
 
 def runtime_versions():

@@ -16,7 +16,8 @@ CDIR = os.path.join(HERE, "csrc")
 SRC = os.path.join(CDIR, "engine.hip")
 UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip", "reg_increment_lock.hip",
          "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip",
-         "reg_spread.hip", "reg_two_phase_live.hip", "reg_spin_lock.hip", "reg_fair_rings.hip"]
+         "reg_spread.hip", "reg_two_phase_live.hip", "reg_spin_lock.hip", "reg_fair_rings.hip", "reg_leads.hip",
+         "reg_req_lock.hip", "reg_req_lock_wide.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
                                                 "dist.hpp", "dist_host.hpp", "sim.hpp", "kernels_sim.hpp", "live.hpp", "kernels_live.hpp", "cover.hpp", "kernels_cover.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
                                                 "actor.hpp", "abd_wide.hpp", "table_selftest.hpp", "kernels_audit.hpp", "rehash_selftest.hpp"]]
@@ -104,7 +105,7 @@ def _library(force, verbose, pool):
         return OUT
 
     # the largest units first, so the slowest compiles start first
-    order = sorted(UNITS, key=lambda u: 0 if u.startswith("reg_paxos") or u.startswith("reg_registers") else 1)
+    order = sorted(UNITS, key=lambda u: 0 if u.startswith(("reg_paxos", "reg_registers", "reg_req_lock")) else 1)
     return [pool.submit(link, [pool.submit(compile_unit, u) for u in order])]
 
 

@@ -18,6 +18,8 @@ class Expectation(enum.IntEnum):
     Always = N.SR_ALWAYS
     Eventually = N.SR_EVENTUALLY
     Sometimes = N.SR_SOMETIMES
+    LeadsTo = N.SR_LEADS_TO  # (no reference counterpart: "whenever the trigger holds, eventually the condition")
+    LEADS_TO = N.SR_LEADS_TO  # (an alias, under the engine's own name for it)
 
 
 class CheckerError(RuntimeError):
@@ -628,12 +630,22 @@ class GpuBfsChecker:
         the state the last state repeats (the closed walk may pass it more than once). A check under
         `strong_fairness()` adds "strong" instead: the dict of sr_live_strong (levels, the depth of the
         decomposition tree, components, all its nodes, fair_components, its fair nodes, and the rest as
-        for "weak")."""
+        for "weak"). For a leads-to property the pass adds "leads": the dict of sr_live_leads (triggered, pending,
+        violating: the reachable states where the trigger holds, those of them where the condition does not, and
+        those of them from which a (fair) run exists on which it never does; trigger_index = trigger_depth: the
+        seed's index on the witness, -1 without one; seed_ms); `witness_len`, `loop_start` and `init_index` are then
+        over the whole path, prefix included, and a fair mode's `stem_len` counts from the seed."""
         r = N.sr_live_result()
         st = self._lib.sr_gpu_bfs_liveness(self._h, self._prop_index(name), ctypes.byref(r))
         if st != 0:
             raise CheckerError("sr_gpu_bfs_liveness", st)
         out = r.as_dict()
+        ld = N.sr_live_leads()
+        st = self._lib.sr_gpu_bfs_liveness_leads(self._h, self._prop_index(name), ctypes.byref(ld))
+        if st != 0:
+            raise CheckerError("sr_gpu_bfs_liveness_leads", st)
+        if ld.ran:
+            out["leads"] = ld.as_dict()
         for mode, stats in (("weak", N.sr_live_weak), ("strong", N.sr_live_strong)):
             if getattr(self, "_" + mode, False) and r.ran:
                 s = stats()
@@ -703,6 +715,21 @@ class GpuBfsChecker:
         r = self.liveness(name)
         return r["loop_start"] if r["ran"] and r["witness_len"] >= 0 and r["loop_start"] >= 0 else None
 
+    def trigger_index(self, name):
+        """`complete_liveness()`: if the leads-to property `name` has a discovery, the index of the path's state
+        at which its trigger holds and from which on its condition never does (the length of the prefix); None
+        otherwise."""
+        ld = self._leads_info(name)
+        return ld["trigger_index"] if ld and ld["trigger_index"] >= 0 else None
+
+    def _leads_info(self, name):
+        """The "leads" dict of `liveness(name)`, or None if the pass did not decide the leads-to property `name`
+        (nothing else does)."""
+        return self.liveness(name).get("leads")
+
+    def _leads_checked(self, name):
+        return bool(self._leads_info(name))
+
     def launch_profile(self):
         """profile(): [(kernel_ms, frontier)] of every expand launch, in launch order."""
         n = self._lib.sr_gpu_bfs_launch_profile(self._h, None, None, 0)
@@ -739,8 +766,19 @@ class GpuBfsChecker:
         self.join()
         w.write(f"Done. states={self.state_count()}, unique={self.unique_state_count()}, "
                 f"sec={int(time.monotonic() - start)}\n")
-        for name, path in self.discoveries().items():
+        found = self.discoveries()
+        for name, path in found.items():
             w.write(f'Discovered "{name}" {self.discovery_classification(name)} {path}')
+        for name, exp in self.properties():  # a leads-to property without a discovery: what the pass found
+            if exp != Expectation.LeadsTo or name in found:
+                continue
+            ld = self._leads_info(name)
+            if not ld:
+                w.write(f'Leads-to "{name}": not checked\n')
+            elif ld["triggered"]:
+                w.write(f'Leads-to "{name}": holds (triggered {ld["triggered"]} states)\n')
+            else:
+                w.write(f'Leads-to "{name}": holds vacuously (never triggered)\n')
         return self
 
     def assert_properties(self):
@@ -763,6 +801,9 @@ class GpuBfsChecker:
             raise AssertionError(f'Unexpected "{name}" {self.discovery_classification(name)} {found}'
                                  f"Last state: {found.last_state()}\n")
         assert self.is_done(), f'Discovery for "{name}" not found, but model checking is incomplete.'
+        if dict(self.properties())[name] == Expectation.LeadsTo and not self._leads_checked(name):
+            raise AssertionError(f'Leads-to property "{name}" was not checked (it takes complete_liveness(), '
+                                 "weak_fairness() or strong_fairness(), and a search that explored everything).")
 
     def replay(self, actions, init_index=0):
         """`Path::from_actions` on the host copy of the model: (states, conditions) or None."""
@@ -814,7 +855,56 @@ class GpuBfsChecker:
         arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
         return self._lib.sr_gpu_bfs_sink_kind(self._h, init, arr, len(ids))
 
-    def assert_discovery(self, name, actions):
+    def _replay_triggers(self, name, actions, init):
+        """The leads-to property's trigger on every state of the path (sr_gpu_bfs_replay_triggers), or None."""
+        ids = [self.action_id(a) for a in actions]
+        arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
+        out = (ctypes.c_int32 * (len(ids) + 1))()
+        n = self._lib.sr_gpu_bfs_replay_triggers(self._h, init, arr, len(ids), self._prop_index(name), out, len(ids) + 1)
+        return None if n < 0 else [bool(x) for x in out[:n]]
+
+    def _assert_leads_discovery(self, name, actions, found, trigger_index, loop_start):
+        """assert_discovery for a leads-to property: from some init state the actions lead, at some index t (the
+        given trigger_index, else any), to a state where the trigger holds; the condition holds on no state from t
+        on; and the path ends as the check's mode allows: at a terminal state, under a fairness mode at a stutter
+        end, or at a state equal to the one at some index j (the given loop_start, else any) with t <= j < the
+        last index, where under weak / strong fairness the loop from j must be fair."""
+        i = self._prop_index(name)
+        info = []
+        for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):
+            r = self.replay_trace(actions, init)
+            trig = self._replay_triggers(name, actions, init) if r is not None else None
+            if r is None or trig is None:
+                continue
+            per_state, terminal = r
+            states, _ = self.replay(actions, init)
+            last = len(states) - 1
+            starts = range(last + 1) if trigger_index is None else [trigger_index]
+            for t in starts:
+                if not 0 <= t <= last or not trig[t]:
+                    info.append(f"the trigger does not hold at index {t}")
+                    continue
+                if any(s[i] for s in per_state[t:]):
+                    info.append(f"the condition holds from index {t} on")
+                    continue
+                if loop_start is None and (terminal or (self._accepts_stutter_ends() and self._sink_kind(actions, init) == N.SR_LIVE_END_STUTTER)):
+                    return
+                for j in (range(t, last) if loop_start is None else [loop_start]):
+                    if not t <= j < last:
+                        info.append(f"loop_start {j} is not in [{t}, {last})")
+                    elif states[j] != states[last]:
+                        continue
+                    elif self._weak and not self._loop_is_fair(actions, init, j):
+                        info.append("the loop is not weakly fair")
+                    elif self._strong and not self._loop_is_fair(actions, init, j, strong=True):
+                        info.append("the loop is not strongly fair")
+                    else:
+                        return
+                info.append(f"from index {t} the path neither ends at a sink nor closes a loop")
+        extra = f" ({'; '.join(sorted(set(info)))})" if info else ""
+        raise AssertionError(f'Invalid discovery for "{name}"{extra}, but a valid one was found. found={found.into_actions()}')
+
+    def assert_discovery(self, name, actions, trigger_index=None, loop_start=None):
         """`assert_discovery` (src/checker.rs:292-337): the actions, from some init state, lead to a
         state violating an `always` / satisfying a `sometimes` property, or along a path on which
         an `eventually` property never holds and that ends at a terminal state. Only a check that can
@@ -824,10 +914,14 @@ class GpuBfsChecker:
         for an `eventually` property, a path that ends at a stutter end (a state with successors that
         all are the state itself), decided on the host model. A check under weak fairness accepts stutter
         ends likewise, and a lasso only if its loop is weakly fair on the host model; a check under strong
-        fairness likewise, and a lasso only if its loop is strongly fair there."""
+        fairness likewise, and a lasso only if its loop is strongly fair there. A leads-to property takes a path
+        by the rule of `_assert_leads_discovery`; trigger_index and loop_start (that kind of property only) pin
+        the two indices instead of leaving them to be found."""
         found = self.assert_any_discovery(name)
         i = self._prop_index(name)
         exp = self.properties()[i][1]
+        if exp == Expectation.LeadsTo:
+            return self._assert_leads_discovery(name, actions, found, trigger_index, loop_start)
         loops = exp == Expectation.Eventually and self._accepts_lassos()
         info = []
         for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):
@@ -995,3 +1089,6 @@ class GpuSimulationChecker(GpuBfsChecker):
 
     def liveness(self, name):
         raise NotImplementedError("liveness: the simulation checker keeps no reachable set (complete_liveness is spawn_bfs's)")
+
+    def _leads_info(self, name):
+        return None  # (a walk decides no leads-to property)

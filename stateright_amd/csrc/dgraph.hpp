@@ -138,4 +138,31 @@ struct DGraph {
     std::string action_name(i64 id) const { return std::to_string(id); }
 };
 
+// LeadsDGraph: DGraph's adjacency from paths plus an explicit list of TRIGGER nodes, for hand-drawn graphs of
+// the leads-to check (live.hpp, LEADS-TO; no reference counterpart). One leads-to property "trigger ~> odd":
+// its target condition is DGraph's "odd", its trigger "the node is in the list". Params (its own format;
+// DGraph's, which the oracle shares, is unchanged): [n_trig, t.., len0, v.., len1, v.., ...].
+struct LeadsDGraph : DGraph {
+    u64 trig[4] = {};
+
+    static LeadsDGraph make(const i64* p, int np, int device) {
+        if (np < 1 || p[0] < 0 || 1 + p[0] > np) throw Error(SR_ERR_ARG, "leads dgraph: needs (n_trig, triggers.., paths...)");
+        const int nt = (int)p[0];
+        std::vector<i64> dp(1, (i64)EVENTUALLY);  // the paths, as DGraph's parameters
+        dp.insert(dp.end(), p + 1 + nt, p + np);
+        LeadsDGraph m;
+        static_cast<DGraph&>(m) = DGraph::make(dp.data(), (int)dp.size(), device);
+        for (int i = 0; i < nt; ++i) {
+            if (p[1 + i] < 0 || p[1 + i] > 255) throw Error(SR_ERR_ARG, "leads dgraph: nodes are u8");
+            m.trig[p[1 + i] / 64] |= 1ull << (p[1 + i] % 64);
+        }
+        return m;
+    }
+    u32 emask() const { return 0u; }
+    SR_HD u32 lmask() const { return 1u; }
+    SR_HD bool leads_from(int, const u64* s) const { return trig[(s[0] & 255) >> 6] >> (s[0] & 63) & 1; }
+    int expectation(int) const { return LEADS_TO; }
+    const char* prop_name(int) const { return "trigger ~> odd"; }
+};
+
 }  // namespace sr

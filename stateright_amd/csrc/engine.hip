@@ -46,6 +46,12 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_2PC_LIVE: return reg_two_phase_live(a);
         case SR_MODEL_SPIN_LOCK: return reg_spin_lock(a);
         case SR_MODEL_FAIR_RINGS: return reg_fair_rings(a);
+        case SR_MODEL_LEADS_GRAPH:
+        case SR_MODEL_LEADS_DGRAPH:
+            return reg_leads(a);
+        case SR_MODEL_REQ_LOCK:
+            req_lock_threads(a.p, a.np);
+            return a.p[0] <= 4 ? reg_req_lock(a) : reg_req_lock_wide(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
@@ -458,6 +464,11 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
             return with_spin_lock(p, np, [&](const auto& m) -> i64 { return f(m); });
         case SR_MODEL_FAIR_RINGS:
             return with_fair_rings(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_LEADS_GRAPH:
+            return with_leads_graph(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_LEADS_DGRAPH: return f(LeadsDGraph::make(p, np, -1));  // (host tables only)
+        case SR_MODEL_REQ_LOCK:
+            return with_req_lock(p, np, [&](const auto& m) -> i64 { return f(m); });
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -778,6 +789,50 @@ int64_t sr_liveness_host_weak(int32_t model, const int64_t* p, int32_t np, int32
     const char* args = !out || !weak || max_states < 1 ? "sr_liveness_host_weak: out, weak and max_states >= 1" : nullptr;
     return liveness_host_entry("sr_liveness_host_weak", args, "weak fairness", model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) {
         return live_host_split(moves ? live_host_weak<true>(m, prop, (u64)max_states) : live_host_weak<false>(m, prop, (u64)max_states), weak);
+    });
+}
+
+int32_t sr_gpu_bfs_liveness_leads(const sr_bfs* b, int32_t prop, sr_live_leads* out) {
+    if (!b || !out || !b->e->finished.load(std::memory_order_acquire) || !b->e->live_leads_result(prop, out)) return SR_ERR_ARG;
+    return SR_OK;
+}
+
+int32_t sr_gpu_bfs_replay_triggers(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t prop, int32_t* out, int32_t cap) {
+    if (!b || n < 0 || (n > 0 && !ids) || !out || cap < n + 1) return -1;
+    try {
+        std::vector<int> t;
+        const int r = b->e->triggers(init, ids, n, prop, t);
+        for (int i = 0; r > 0 && i < r; ++i) out[i] = t[i];
+        return r;
+    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
+        set_error(x.what());
+        return -1;
+    }
+}
+
+int64_t sr_liveness_host_leads(int32_t model, const int64_t* p, int32_t np, int32_t prop, int32_t fairness, int64_t max_states,
+                               sr_live_result* out, sr_live_leads* leads, int64_t* action_ids, int32_t cap) {
+    const char* args = !out || !leads || max_states < 1 ? "sr_liveness_host_leads: out, leads and max_states >= 1"
+                       : fairness < 0 || fairness > 3  ? "sr_liveness_host_leads: fairness must be 0 (none), 1 (progress), 2 (weak) or 3 (strong)"
+                                                       : nullptr;
+    if (leads) *leads = live_leads_none();
+    const char* mode = fairness == 2 ? "weak fairness" : fairness == 3 ? "strong fairness" : nullptr;
+    return liveness_host_entry("sr_liveness_host_leads", args, mode, model, p, np, out, action_ids, cap, [&](const auto& m, bool moves) -> LiveHost {
+        using M = std::decay_t<decltype(m)>;
+        if constexpr (!has_lmask<M>::value) {
+            throw Error(SR_ERR_ARG, "liveness: the model has no leads-to property");
+        } else {
+            const LiveLeadsStart start{prop, *leads};
+            const u64 cap_states = (u64)max_states;
+            sr_live_weak wk;
+            sr_live_strong sg;
+            switch (fairness) {
+                case 0: return live_host<false, true>(m, prop, cap_states, start);
+                case 1: return moves ? live_host<true, true>(m, prop, cap_states, start) : live_host<true, false>(m, prop, cap_states, start);
+                case 2: return live_host_split(moves ? live_host_weak<true>(m, prop, cap_states, start) : live_host_weak<false>(m, prop, cap_states, start), &wk);
+                default: return live_host_split(moves ? live_host_strong<true>(m, prop, cap_states, start) : live_host_strong<false>(m, prop, cap_states, start), &sg);
+            }
+        }
     });
 }
 

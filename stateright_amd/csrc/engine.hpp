@@ -100,6 +100,12 @@ class EngineBase {
         (void)init, (void)ids, (void)n, (void)loop_start, (void)strong;
         return -1;
     }
+    // The trigger of the leads-to property p on every state of the path that the actions describe from init state
+    // `init` (sr_gpu_bfs_replay_triggers): n + 1 entries; -1: no such path, or p is no leads-to property.
+    virtual int triggers(int init, const i64* ids, int n, int p, std::vector<int>& out) const {
+        (void)init, (void)ids, (void)n, (void)p, (void)out;
+        return -1;
+    }
     // The strong-fairness figures of that check (sr_gpu_bfs_liveness_strong); false: p is no property.
     bool live_strong_result(int p, sr_live_strong* out) const {
         if (p < 0 || p >= nprops()) return false;
@@ -110,6 +116,13 @@ class EngineBase {
     std::vector<sr_live_result> live;  // per property (empty: the pass never ran)
     std::vector<sr_live_weak> live_weak;  // per property (empty: the pass never ran in the weak mode)
     std::vector<sr_live_strong> live_strong;  // per property (empty: the pass never ran in the strong mode)
+    std::vector<sr_live_leads> live_leads;  // per property (empty: the pass never ran; ran = 0: no leads-to property)
+    // The leads-to figures of that check (sr_gpu_bfs_liveness_leads); false: p is no property.
+    bool live_leads_result(int p, sr_live_leads* out) const {
+        if (p < 0 || p >= nprops()) return false;
+        *out = p < (int)live_leads.size() ? live_leads[p] : live_leads_none();
+        return true;
+    }
     CoverFigures cover;  // the coverage pass' figures (cover.hpp; c.ran = 0: it did not run)
     std::atomic<u64> state_count{0}, unique{0};
     std::atomic<u32> max_depth{0};
@@ -191,6 +204,30 @@ int loop_fair_model(const M& m, int init, const i64* ids, int n, int loop_start,
         const u64* loop = &path[(size_t)loop_start * W];
         return (strong ? live_loop_strong_fair(m, loop, (size_t)(n - loop_start)) : live_loop_fair(m, loop, (size_t)(n - loop_start))) ? 1 : 0;
     }
+}
+
+// sr_gpu_bfs_replay_triggers: the actions are replayed from init state `init` as sink_kind_model replays them;
+// out takes leads_from(p, .) of every state of the path. -1: no such path, or p is no leads-to property.
+template <class M>
+int triggers_model(const M& m, int init, const i64* ids, int n, int p, std::vector<int>& out) {
+    constexpr int W = M::W;
+    out.clear();
+    if (p < 0 || p >= M::NPROPS || !(model_lmask(m) >> p & 1)) return -1;
+    const std::vector<u64> inits = init_states_of(m);
+    if (init < 0 || init >= (int)(inits.size() / W)) return -1;
+    std::vector<u64> cur(&inits[(size_t)init * W], &inits[(size_t)init * W] + W);
+    out.push_back(live_leads_from(m, p, cur.data()) ? 1 : 0);
+    for (int i = 0; i < n; ++i) {
+        bool found = false;
+        std::vector<u64> nx;
+        for_each_successor(m, cur.data(), [&](int a, const u64* ns) {
+            if (!found && m.action_id(cur.data(), a) == ids[i]) nx.assign(ns, ns + W), found = true;
+        });
+        if (!found) return -1;
+        cur = nx;
+        out.push_back(live_leads_from(m, p, cur.data()) ? 1 : 0);
+    }
+    return n + 1;
 }
 
 template <class M>
@@ -392,8 +429,9 @@ class Engine final : public EngineBase {
 
   public:
     Engine(M m, const sr_opts& o)
-        : m_(m), o_(o), A_((u32)m.max_actions()), D_((u32)m.max_out_degree()), emask_(model_emask(m)) {
+        : m_(m), o_(o), A_((u32)m.max_actions()), D_((u32)m.max_out_degree()), emask_(model_emask(m)), lmask_(model_lmask(m)) {
         disc.resize(M::NPROPS);
+        if (emask_ & lmask_) throw Error(SR_ERR_ARG, "a leads-to property is in the model's emask()");
         (void)init_states_of(m_);  // a model with more init states than it declares fails at spawn
         if (o_.liveness) {  // the complete `eventually` check (live.hpp): what it cannot be combined with
             if (o_.target_state_count)
@@ -552,6 +590,9 @@ class Engine final : public EngineBase {
     int sink_kind(int init, const i64* ids, int n) const override { return sink_kind_model(base_model(m_), init, ids, n); }
     int loop_fair(int init, const i64* ids, int n, int loop_start, bool strong) const override {
         return loop_fair_model(base_model(m_), init, ids, n, loop_start, strong);
+    }
+    int triggers(int init, const i64* ids, int n, int p, std::vector<int>& out) const override {
+        return triggers_model(base_model(m_), init, ids, n, p, out);
     }
     int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                 std::vector<i64>& states) const override {
@@ -1018,6 +1059,7 @@ class Engine final : public EngineBase {
         live.clear();
         live_weak.clear();
         live_strong.clear();
+        live_leads.clear();
         live_path_.assign(M::NPROPS, {});
         cover = CoverFigures{};
         cover.c = cover_none();
@@ -1066,7 +1108,7 @@ class Engine final : public EngineBase {
         ensure_arena(std::max<u64>(std::max<u64>(1u << 16, arena0), (o_.capacity_hint + slack + 1024) * grow_factor_), 0);
         lstart_.assign({0, (u64)k});
         lvisited_.clear();
-        const u32 und0 = ((1u << M::NPROPS) - 1) & ~emask_;
+        const u32 und0 = ((1u << M::NPROPS) - 1) & ~emask_ & ~lmask_;  // (no kernel of the search sees a leads-to bit)
         u32 sq = 0;
         if ((u64)k * W <= ROOTS_INLINE_WORDS) {
             // one launch: counters reset, level 0 into the arena (no parents; `eventually` bits
@@ -1099,13 +1141,20 @@ class Engine final : public EngineBase {
         SR_HIP(hipGetLastError());
         // FAST pipelined order: level 0 is enqueued before the host reads the roots' outcome (it is
         // ignored if the roots already discover every property)
-        const bool pipelined = !fifo_ && !emask_ && !o_.target_state_count && M::NPROPS > 0 && pipeline_;
+        // (a model with leads-to properties takes the level loop below: its host mask differs from the kernels')
+        const bool pipelined = !fifo_ && !emask_ && !lmask_ && !o_.target_state_count && M::NPROPS > 0 && pipeline_;
         const u32 sq_level0 = pipelined ? launch_sync((u64)k, (1u << M::NPROPS) - 1) : 0u;
         wait_publish(sq);
         state_count = (u64)k;
         unique = lc_.claims;
 
-        u32 undiscovered = (1u << M::NPROPS) - 1;
+        // A leads-to property is decided by the liveness pass alone: with the pass on, the host keeps its bit, so
+        // that the search explores everything as for an undiscovered `always`; with it off the bit is dropped and
+        // the search stops as if the property were absent.
+        u32 undiscovered = ((1u << M::NPROPS) - 1) & ~(o_.liveness ? 0u : lmask_);
+        // A model whose properties are all leads-to, with the pass off, has nothing for the search to await: it is
+        // a model without properties (below: the first pop returns, bfs.rs:226), not an early exit inside a level.
+        const bool no_props = M::NPROPS == 0 || undiscovered == 0;
         u64 n = (u64)k, popped_before = 0;
         u32 level = 0;
         bool order_dependent = false;
@@ -1143,7 +1192,7 @@ class Engine final : public EngineBase {
             }
             u64 limit = n, visited = n;
             bool stop = false;
-            if (M::NPROPS == 0) {
+            if (no_props) {
                 limit = 0;
                 visited = std::min<u64>(1, n);
                 stop = true;
@@ -1204,7 +1253,7 @@ class Engine final : public EngineBase {
                 SR_HIP(stream_sync(stream_));
             }
             if (limit) {
-                produced = expand_level(level, n, limit, undiscovered & ~emask_, peb.p);
+                produced = expand_level(level, n, limit, undiscovered & ~emask_ & ~lmask_, peb.p);
             } else {
                 std::memset(&lc_, 0, sizeof(lc_));
             }
@@ -1532,10 +1581,11 @@ class Engine final : public EngineBase {
         live.assign(M::NPROPS, live_result_none());
         live_weak.assign(M::NPROPS, live_fair_none<sr_live_weak>());
         live_strong.assign(M::NPROPS, live_fair_none<sr_live_strong>());
-        if constexpr (has_emask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
-            u32 todo = 0;
+        live_leads.assign(M::NPROPS, live_leads_none());
+        if constexpr ((has_emask<M>::value || has_lmask<M>::value) && !is_canon<M>::value && !is_evbits<M>::value) {
+            u32 todo = 0;  // the `eventually` properties without a discovery, and the leads-to properties
             for (int p = 0; p < M::NPROPS; ++p)
-                if ((emask_ >> p & 1) && !disc[p].found) todo |= 1u << p;
+                if (((emask_ | lmask_) >> p & 1) && !disc[p].found) todo |= 1u << p;
             if (!todo) return;
             if (lstart_.back() > 0xffffffffull)
                 throw Error(SR_ERR_UNSUPPORTED, "liveness with more than 2^32 - 1 unique states: the pass indexes the arena with 32 bits");
@@ -1574,6 +1624,7 @@ class Engine final : public EngineBase {
                 const auto t0 = Clock::now();
                 sr_live_result& r = live[p];
                 r.ran = 1;
+                sr_live_leads* const leads = lmask_ >> p & 1 ? &live_leads[p] : nullptr;  // (a leads-to property: live.hpp LEADS-TO)
                 SR_HIP(hipMemsetAsync(alive.p, 0, bwords * sizeof(u32), stream_));
                 SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
                 live_mark<M><<<blocks_for(n, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, n, t, p, slot_of.p, alive.p, wl[0].p, lc);
@@ -1610,21 +1661,30 @@ class Engine final : public EngineBase {
                 }
                 if (weak || strong) {
                     live_fair_pass(strong, LivePassArgs{p, r, n, t, bwords, slot_of.p, alive.p, np_list.p, np_cnt, wl[last].p, cnt, wl[last ^ 1].p,
-                                                        inits, k, walk_steps});
+                                                        inits, k, walk_steps, leads});
                     r.pass_ms = secs(t0, Clock::now()) * 1e3;
                     continue;
                 }
-                // the init state of lowest index whose bit survived (one launch, one read-back)
-                SR_HIP(hipMemsetAsync(&lc->first_init, 0xff, sizeof(u32), stream_));
-                live_first_init<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of.p, alive.p, k, lc);
-                read_back();
-                if (h.first_init < k) r.init_index = (int32_t)h.first_init;
-                if (r.init_index >= 0) {
+                std::vector<u64> path;  // the witness' states: the walk's first state, behind a leads-to prefix
+                u32 seed = ~0u;         // a leads-to property: the seed's arena index
+                if (leads) {
+                    seed = live_leads_seed<false>(p, n, k, slot_of.p, alive.p, nullptr, nullptr, *leads);
+                    if (seed != ~0u) live_leads_prefix(seed, inits, r, path);
+                } else {
+                    // the init state of lowest index whose bit survived (one launch, one read-back)
+                    SR_HIP(hipMemsetAsync(&lc->first_init, 0xff, sizeof(u32), stream_));
+                    live_first_init<><<<1, LIVE_BLOCK, 0, stream_>>>(slot_of.p, alive.p, k, lc);
+                    read_back();
+                    if (h.first_init < k) r.init_index = (int32_t)h.first_init;
+                    if (r.init_index >= 0) path.assign(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
+                }
+                if (!path.empty()) {
+                    const size_t off = path.size() / W - 1;  // the walk starts at this index of the path
                     if (!onpath.p) onpath.alloc(o_.device, bwords);
                     if (!out.p) out.alloc(o_.device, ((size_t)walk_steps + 1) * W);
                     SR_HIP(hipMemsetAsync(onpath.p, 0, bwords * sizeof(u32), stream_));
-                    std::vector<u64> path(&inits[(size_t)r.init_index * W], &inits[(size_t)r.init_index * W] + W);
-                    SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
+                    if (leads) SR_HIP(hipMemcpyAsync(out.p, arena_.p + (size_t)seed * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+                    else SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, stream_));
                     for (u32 resume = 0;; resume = 1) {  // (each launch but the last takes walk_steps steps; |F_p| in all)
                         SR_HIP(hipMemsetAsync(lc, 0, sizeof(LiveCounters), stream_));
                         if (fair) live_walk<M, true><<<1, 64, 0, stream_>>>(m_, t, alive.p, onpath.p, out.p, walk_steps, resume, lc);
@@ -1635,14 +1695,14 @@ class Engine final : public EngineBase {
                         path.resize(o + (size_t)h.steps * W);
                         if (h.steps)
                             SR_HIP(hipMemcpy(&path[o], out.p + W, (size_t)h.steps * W * sizeof(u64), hipMemcpyDeviceToHost));
-                        if (path.size() / W - 1 > r.surviving)
+                        if (path.size() / W - 1 - off > r.surviving)
                             throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness is longer than the fixpoint has states");
                         if (h.end != LIVE_WALK_MORE) break;
                         if (!h.steps) throw Error(SR_ERR_HIP, "liveness: a witness launch made no step");
                         SR_HIP(hipMemcpyAsync(out.p, out.p + (size_t)h.steps * W, W * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
                     }
                     if (h.end == LIVE_WALK_STUTTER && !fair) throw Error(SR_ERR_HIP, "liveness: a witness ends at a stutter end with the mode off");
-                    live_accept(p, r, path, h.end, fair);
+                    live_accept(p, r, path, h.end, fair, off);
                 }
                 r.pass_ms = secs(t0, Clock::now()) * 1e3;
             }
@@ -1656,12 +1716,15 @@ class Engine final : public EngineBase {
     // 64-bit fingerprints. Under progress fairness (fair) also: no step returns its own state, and a
     // path that is no lasso ends at a terminal state or at a stutter end, which has at least one
     // successor and whose successors all are the state itself.
-    void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, u32 end, bool fair) {
+    // off: the index of the witness' own first state on the path (a leads-to property: behind its prefix, live.hpp
+    // LEADS-TO; 0 otherwise). The loop closes on a state from there on: one that closes on a prefix state only is
+    // an engine error, reported as the collision below.
+    void live_accept(int p, sr_live_result& r, const std::vector<u64>& path, u32 end, bool fair, size_t off = 0) {
         const size_t len = path.size() / W - 1;
-        const std::string name = live_replay(p, path, fair);
+        const std::string name = live_replay(p, path, fair, off);
         const u64* last = &path[len * W];
         if (end == LIVE_WALK_LOOP) {
-            size_t j = 0;
+            size_t j = off;
             while (j < len && !std::equal(last, last + W, &path[j * W])) ++j;
             if (j == len)
                 throw Error(SR_ERR_NONDETERMINISM, "liveness: fingerprint collision: the witness of \"" + name + "\" ended as a loop at step " +
@@ -1688,9 +1751,10 @@ class Engine final : public EngineBase {
     // with fair = true, the last state equals the state at loop_start word for word, and the loop is weakly fair
     // on its own states and steps (live.hpp live_loop_fair); strong: strongly fair (live_loop_strong_fair). A
     // path that fails is an engine error, never a discovery.
-    void live_accept_loop(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start, bool strong) {
+    void live_accept_loop(int p, sr_live_result& r, const std::vector<u64>& path, size_t loop_start, bool strong, size_t off = 0) {
         const size_t len = path.size() / W - 1;
-        const std::string name = live_replay(p, path, true);
+        const std::string name = live_replay(p, path, true, off);
+        if (loop_start < off) throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" starts on its prefix");
         if (loop_start >= len || !std::equal(&path[len * W], &path[len * W] + W, &path[loop_start * W]))
             throw Error(SR_ERR_NONDETERMINISM, "liveness: the closed walk of the witness of \"" + name + "\" does not end where it starts");
         if (strong ? !live_loop_strong_fair(m_, &path[loop_start * W], len - loop_start)
@@ -1704,16 +1768,21 @@ class Engine final : public EngineBase {
 
     // What every acceptance checks first: every step is a successor in `actions()` order (concrete_path), the
     // condition of p holds on no state, and (fair) no step returns its own state. The property's name.
-    std::string live_replay(int p, const std::vector<u64>& path, bool fair) {
+    // A leads-to property (off: its trigger_index): the steps are checked over the whole path, the trigger holds at
+    // off, and the condition and the self-loop checks apply from off on (the condition may hold on the prefix).
+    std::string live_replay(int p, const std::vector<u64>& path, bool fair, size_t off = 0) {
         const size_t len = path.size() / W - 1;
         const std::string name = m_.prop_name(p);
         std::vector<i64> acts, described;
         concrete_path(m_, path, acts, described);
-        for (size_t i = 0; i <= len; ++i)
+        if (off > len) throw Error(SR_ERR_NONDETERMINISM, "liveness: the witness of \"" + name + "\" is shorter than its prefix");
+        if ((lmask_ >> p & 1) && !live_leads_from(m_, p, &path[off * W]))
+            throw Error(SR_ERR_NONDETERMINISM, "liveness: the trigger of \"" + name + "\" does not hold at step " + std::to_string(off) + " of its witness");
+        for (size_t i = off; i <= len; ++i)
             if (!live_not_p(m_, p, &path[i * W]))
                 throw Error(SR_ERR_NONDETERMINISM, "liveness: \"" + name + "\" holds at step " + std::to_string(i) + " of its witness");
         if (fair)
-            for (size_t i = 0; i < len; ++i)
+            for (size_t i = off; i < len; ++i)
                 if (std::equal(&path[i * W], &path[i * W] + W, &path[(i + 1) * W]))
                     throw Error(SR_ERR_NONDETERMINISM, "liveness: step " + std::to_string(i) + " of the witness of \"" + name +
                                                            "\" returns its own state (a fair mode steps over no self-loop)");
@@ -1744,7 +1813,67 @@ class Engine final : public EngineBase {
         u32* spare;
         const std::vector<u64>& inits;
         u32 k, walk_steps;
+        sr_live_leads* leads;  // a leads-to property's figures (nullptr: an `eventually` property)
     };
+
+    // LEADS-TO (live.hpp; kernels_live.hpp live_leads_scan, live_leads_min): the three counts and the seed of
+    // property p over the arena's n states, behind the mode's stages for its condition. RANKED: X_Q is FairF (idx,
+    // rank); otherwise the alive bitmap. Returns the seed's arena index (~0: no violating state). One read-back for
+    // the counts; then W + 1 launches over the seed's level, enqueued back to back, and one more read-back.
+    template <bool RANKED>
+    u32 live_leads_seed(int p, u32 n, u32 k, const u64* slot_of, const u32* alive, const u32* idx, const u32* rank, sr_live_leads& L) {
+        if constexpr (has_lmask<M>::value) {
+            const auto t0 = Clock::now();
+            DBuf<u64> buf;  // [LiveLeadsCounters | the seed's W words | its arena index]
+            constexpr size_t CW = sizeof(LiveLeadsCounters) / 8;
+            static_assert(sizeof(LiveLeadsCounters) == 16, "LiveLeadsCounters: four u32");
+            buf.alloc(o_.device, CW + W + 1);
+            LiveLeadsCounters* lc = reinterpret_cast<LiveLeadsCounters*>(buf.p);
+            u64* seed_w = buf.p + CW;
+            u32* seed_i = reinterpret_cast<u32*>(buf.p + CW + W);
+            SR_HIP(hipMemsetAsync(buf.p, 0xff, (CW + W + 1) * sizeof(u64), stream_));
+            SR_HIP(hipMemsetAsync(lc, 0, 3 * sizeof(u32), stream_));
+            live_leads_scan<M, RANKED><<<std::min(blocks_for(n, LIVE_BLOCK), LIVE_LEADS_GRID), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, n, k, p, slot_of, alive, idx, rank, lc);
+            SR_HIP(hipGetLastError());
+            LiveLeadsCounters h{};
+            SR_HIP(hipMemcpyAsync(&h, lc, sizeof(h), hipMemcpyDeviceToHost, stream_));
+            SR_HIP(stream_sync(stream_));
+            L.ran = 1;
+            L.triggered = h.triggered;
+            L.pending = h.pending;
+            L.violating = h.violating;
+            u32 seed = ~0u;
+            if (h.violating) {
+                if (h.min_idx >= n) throw Error(SR_ERR_HIP, "liveness: the seed scan counts violating states and names none");
+                // the level of the lowest violating arena index is the lowest depth of a violating state
+                const size_t level = (size_t)(std::upper_bound(lstart_.begin(), lstart_.end(), (u64)h.min_idx) - lstart_.begin()) - 1;
+                const u32 lo = (u32)lstart_[level], hi = (u32)lstart_[level + 1];
+                for (int j = 0; j <= W; ++j)
+                    live_leads_min<M, RANKED><<<blocks_for(hi - lo, LIVE_BLOCK), LIVE_BLOCK, 0, stream_>>>(m_, arena_.p, lo, hi, p, slot_of, alive, idx,
+                                                                                                        rank, j, seed_w, seed_i);
+                SR_HIP(hipGetLastError());
+                SR_HIP(hipMemcpyAsync(&seed, seed_i, sizeof(u32), hipMemcpyDeviceToHost, stream_));
+                SR_HIP(stream_sync(stream_));
+                if (seed < lo || seed >= hi) throw Error(SR_ERR_HIP, "liveness: the tie-break found no seed in the level of the lowest violating state");
+                L.trigger_index = L.trigger_depth = (int64_t)level;
+            }
+            L.seed_ms = secs(t0, Clock::now()) * 1e3;
+            return seed;
+        } else {
+            (void)p, (void)n, (void)k, (void)slot_of, (void)alive, (void)idx, (void)rank, (void)L;
+            return ~0u;
+        }
+    }
+
+    // The prefix of a leads-to witness: the search's own tree path from an init state to the seed (its states into
+    // path, the seed last), and the lowest index of an init state equal to its first state into r.init_index.
+    void live_leads_prefix(u32 seed, const std::vector<u64>& inits, sr_live_result& r, std::vector<u64>& path) {
+        const size_t level = (size_t)(std::upper_bound(lstart_.begin(), lstart_.end(), (u64)seed) - lstart_.begin()) - 1;
+        tree_path((u32)level, (u32)(seed - lstart_[level]), path);
+        for (size_t i = 0; i < inits.size() / W && r.init_index < 0; ++i)
+            if (std::equal(&inits[i * W], &inits[i * W] + W, path.begin())) r.init_index = (int32_t)i;
+        if (r.init_index < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: the prefix of a leads-to witness starts at no init state");
+    }
 
     // WEAK and STRONG FAIRNESS (live.hpp; the kernels' headers in kernels_live.hpp): what the two passes share,
     // each stage written once. `bits` is the bitmap of the set the component search runs on (the weak mode's U,
@@ -1770,6 +1899,8 @@ class Engine final : public EngineBase {
         u32 cnt = 0, round = 0;
         std::vector<u64> path;  // the witness' states
         u64 bound = 0;          // and how many steps it may have
+        size_t off = 0;         // a leads-to property: the length of the prefix the path starts with (first_seed)
+        u32 seed = ~0u;         //                      and the seed's arena index
         u32 g = 0, root = ~0u;  // the stem's last state and its component (by arena index)
         u64 c_mask[MW];         // acc_me of that component
 
@@ -1911,6 +2042,17 @@ class Engine final : public EngineBase {
             return a.r.init_index >= 0;
         }
 
+        // A leads-to property, in place of first_ranked(): the counts, the seed among the states with a rank, and the
+        // prefix into `path`; whether there is a seed.
+        bool first_seed() {
+            seed = e.template live_leads_seed<true>(a.p, a.n, a.k, a.slot_of, a.alive, idx.p, rank.p, *a.leads);
+            if (seed == ~0u) return false;
+            e.live_leads_prefix(seed, a.inits, a.r, path);
+            off = path.size() / W - 1;
+            return true;
+        }
+        bool first() { return a.leads ? first_seed() : first_ranked(); }
+
         // From the path's last state down the ranks rk to rank 0, then slot `then` (each launch but the last
         // takes walk_steps steps).
         void descend(const u32* rk, int then, u32 all) {
@@ -1938,11 +2080,15 @@ class Engine final : public EngineBase {
         bool stem() {
             const std::vector<u64>& inits = a.inits;
             out.alloc(e.o_.device, ((size_t)a.walk_steps + 2) * W);
-            path.assign(&inits[(size_t)a.r.init_index * W], &inits[(size_t)a.r.init_index * W] + W);
-            SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, e.stream_));
-            bound = ((u64)e.A_ + 2) * (a.r.surviving + 1);  // the stem and A + 1 segments, each a simple path
+            if (a.leads) {  // (first_seed: the path holds the prefix, the seed last)
+                SR_HIP(hipMemcpyAsync(out.p, e.arena_.p + (size_t)seed * W, W * sizeof(u64), hipMemcpyDeviceToDevice, e.stream_));
+            } else {
+                path.assign(&inits[(size_t)a.r.init_index * W], &inits[(size_t)a.r.init_index * W] + W);
+                SR_HIP(hipMemcpyAsync(out.p, path.data(), W * sizeof(u64), hipMemcpyHostToDevice, e.stream_));
+            }
+            bound = off + ((u64)e.A_ + 2) * (a.r.surviving + 1);  // the stem and A + 1 segments, each a simple path
             descend(rank.p, -1, 0);
-            s.stem_len = (int64_t)(path.size() / W - 1);
+            s.stem_len = (int64_t)(path.size() / W - 1 - off);
             g = hw.last_idx;
             if (g >= a.n) throw Error(SR_ERR_HIP, "liveness: the stem's last state has no arena index");
             SR_HIP(hipMemcpy(&root, comp.p + g, sizeof(u32), hipMemcpyDeviceToHost));
@@ -1950,7 +2096,7 @@ class Engine final : public EngineBase {
                 u64 all = 0;
                 for_each_successor(e.m_, &path[path.size() - W], [&](int, const u64*) { ++all; });
                 s.loop_len = 0;
-                e.live_accept(a.p, a.r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true);
+                e.live_accept(a.p, a.r, path, all ? LIVE_WALK_STUTTER : LIVE_WALK_TERMINAL, true, off);
                 return false;
             }
             if (root >= a.n) throw Error(SR_ERR_HIP, "liveness: the stem ends in a component without a root");
@@ -1986,8 +2132,8 @@ class Engine final : public EngineBase {
                 if (pl != LIVE_PLAN_SKIP) segment(pl, slot);
             }
             segment(LIVE_PLAN_HOME, 0);
-            s.loop_len = (int64_t)(path.size() / W - 1) - s.stem_len;
-            e.live_accept_loop(a.p, a.r, path, (size_t)s.stem_len, strong);
+            s.loop_len = (int64_t)(path.size() / W - 1 - off) - s.stem_len;
+            e.live_accept_loop(a.p, a.r, path, off + (size_t)s.stem_len, strong, off);
         }
     };
 
@@ -2033,7 +2179,7 @@ class Engine final : public EngineBase {
             sn = f.hw.next_n;
         }
         if (wk.goal_states) f.reach(f.rank.p, f.L, f.X, sn);
-        if (f.first_ranked() && f.stem())
+        if (f.first() && f.stem())
             f.closed_walk([&](int s) { return live_loop_plan(s, f.hw.notme, f.hw.taken, f.c_mask); }, true, false);
         wk.pass_ms = secs(f.t0, Clock::now()) * 1e3;
     }
@@ -2091,7 +2237,7 @@ class Engine final : public EngineBase {
             if (f.hw.goal < frozen) throw Error(SR_ERR_HIP, "liveness: the goal set lost a frozen state");
         }
         if (sg.goal_states) f.reach(f.rank.p, f.L, f.X, sn);
-        if (f.first_ranked() && f.stem())
+        if (f.first() && f.stem())
             f.closed_walk([&](int s) { return live_strong_plan(s, f.hw.taken, f.c_mask); }, false, true);
         sg.pass_ms = secs(f.t0, Clock::now()) * 1e3;
     }
@@ -2404,6 +2550,7 @@ class Engine final : public EngineBase {
     u32 A_;  // action slots
     u32 D_;  // max successors of one state (bounds the new states a chunk can create)
     u32 emask_;  // the model's `eventually` properties
+    u32 lmask_;  // the model's leads-to properties (live.hpp LEADS-TO): never in a kernel's `undiscovered`
     bool fifo_ = false;
     int probe_batch_ = 0;  // SR_PROBE_BATCH: 1 forces the probe rounds, -4 the per-lane probe queues (0: probe_loop)
     // expand_fast's probe loop (DESIGN.md §3 "Probe loops"): rounds of one successor per lane, or

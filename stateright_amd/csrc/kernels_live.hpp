@@ -801,4 +801,116 @@ __global__ void __launch_bounds__(LIVE_BLOCK) live_goal_strong(const u32* __rest
     if (gm && (threadIdx.x & 63) == 0) atomicAdd(&lc->goal, (u32)__popcll(gm));
 }
 
+// ---- leads-to (live.hpp: LEADS-TO). Launched only for a leads-to property, in every mode, behind the mode's
+// own stages for the condition Q (live_mark and the trim; in a fair mode also the components and the ranks),
+// in place of live_first_init / live_first_ranked, which stay the kernels they are. RANKED says how "s is in
+// X_Q" is answered: false, the alive bit at the state's slot (F_p, F_p'); true, a rank at the arena index that
+// the slot maps to (FairF). Neither kernel probes the visited set: a state's slot is live_mark's slot_of.
+//   live_leads_scan  per arena state: the trigger, the condition and the membership test (live_leads_class). A
+//                    lane strides over the arena (a grid of at most LIVE_LEADS_GRID workgroups) and keeps its
+//                    three counts and its lowest violating arena index in registers; at its end a wave reduces
+//                    them by shuffles and issues one atomic per counter that is not zero, and one atomicMin. All
+//                    waves add to the same four words, and atomics on one address are served one after the
+//                    other: with one lane per state (209 K waves on 13.4 M states) they were 5.1-6.7 ms of a
+//                    stage whose reads take a tenth of that (profiles/leads_pass.txt). Level 0 of the arena
+//                    holds the init states as given, duplicates too: of equal init states (equal slots) only
+//                    the one of lowest arena index counts.
+//   live_leads_min   one lane per state of ONE level (the level of that lowest index, which the host reads off
+//                    its level offsets): round j < W takes the minimum of word j over the violating states that
+//                    match the seed's words fixed so far (a wave-level reduction, then one 64-bit atomicMin per
+//                    wave); for one-word states that is one round. Round j = W takes the lowest arena index of
+//                    the state that matches all W words (equal init states: any of them has the same path).
+
+constexpr u32 LIVE_LEADS_GRID = 2048;  // workgroups of live_leads_scan at most (8 per CU)
+
+struct LiveLeadsCounters {
+    u32 triggered, pending, violating;
+    u32 min_idx;  // the lowest arena index of a violating state (~0 before the launch)
+};
+
+template <bool RANKED>
+__device__ __forceinline__ bool live_in_x(u64 slot, const u32* alive, const u32* __restrict__ idx, const u32* __restrict__ rank) {
+    if constexpr (RANKED) {
+        const u32 j = idx[slot];
+        return j != ~0u && rank[j] != ~0u;
+    } else {
+        return live_bit(alive, slot);
+    }
+}
+
+// k: the init states (level 0 is the arena's first k states).
+template <class M, bool RANKED>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_leads_scan(M m, const u64* __restrict__ arena, u32 n, u32 k, int p,
+                                                              const u64* __restrict__ slot_of, const u32* alive,
+                                                              const u32* __restrict__ idx, const u32* __restrict__ rank,
+                                                              LiveLeadsCounters* lc) {
+    u32 nt = 0, np = 0, nv = 0, lowest = ~0u;
+    for (u64 g = blockIdx.x * LIVE_BLOCK + threadIdx.x; g < n; g += (u64)gridDim.x * LIVE_BLOCK) {  // (64 bits: n may be near 2^32)
+        const u32 i = (u32)g;
+        const u64 sl = slot_of[i];
+        bool dup = false;
+        if (i < k)
+            for (u32 j = 0; j < i; ++j) dup = dup || slot_of[j] == sl;
+        if (dup) continue;
+        u64 s[M::W];
+        load_state<M::W>(arena, i, s);
+        const u32 c = live_leads_class(m, p, s, [&] { return live_in_x<RANKED>(sl, alive, idx, rank); });
+        nt += c & LIVE_LEADS_TRIGGERED ? 1u : 0u;
+        np += c & LIVE_LEADS_PENDING ? 1u : 0u;
+        if (c & LIVE_LEADS_VIOLATING) nv += 1, lowest = min(lowest, i);
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {  // (every lane is back here: the loop's trip counts differ by one at most)
+        nt += __shfl_xor(nt, d, 64);
+        np += __shfl_xor(np, d, 64);
+        nv += __shfl_xor(nv, d, 64);
+        lowest = min(lowest, (u32)__shfl_xor(lowest, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (nt) atomicAdd(&lc->triggered, nt);
+        if (np) atomicAdd(&lc->pending, np);
+        if (nv) atomicAdd(&lc->violating, nv), atomicMin(&lc->min_idx, lowest);
+    }
+}
+
+// The states lo .. hi - 1 of the arena (one level). seed: W words, all ones before round 0; seed_idx: ~0 before
+// round W.
+template <class M, bool RANKED>
+__global__ void __launch_bounds__(LIVE_BLOCK) live_leads_min(M m, const u64* __restrict__ arena, u32 lo, u32 hi, int p,
+                                                             const u64* __restrict__ slot_of, const u32* alive,
+                                                             const u32* __restrict__ idx, const u32* __restrict__ rank, int j,
+                                                             u64* seed, u32* seed_idx) {
+    constexpr int W = M::W;
+    const u64 g = (u64)lo + (u64)blockIdx.x * LIVE_BLOCK + threadIdx.x;  // (64 bits: hi may be near 2^32)
+    const u32 i = (u32)g;
+    bool cand = false;
+    u64 s[W];
+#pragma unroll
+    for (int x = 0; x < W; ++x) s[x] = ~0ull;
+    if (g < hi) {
+        load_state<W>(arena, i, s);
+        const u64 sl = slot_of[i];
+        cand = (live_leads_class(m, p, s, [&] { return live_in_x<RANKED>(sl, alive, idx, rank); }) & LIVE_LEADS_VIOLATING) != 0;
+#pragma unroll
+        for (int x = 0; x < W; ++x)
+            if (x < j) cand = cand && s[x] == seed[x];
+    }
+    const u64 cm = __ballot(cand);
+    if (!cm) return;
+    if (j >= W) {
+        if ((int)(threadIdx.x & 63) == __builtin_ctzll(cm)) atomicMin(seed_idx, i);
+        return;
+    }
+    u64 v = ~0ull;
+#pragma unroll
+    for (int x = 0; x < W; ++x)  // (no dynamic index: the state stays in registers)
+        if (x == j && cand) v = s[x];
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        const u64 o = (u64)__shfl_xor((unsigned long long)v, d, 64);
+        v = o < v ? o : v;
+    }
+    if ((int)(threadIdx.x & 63) == __builtin_ctzll(cm)) atomicMin((unsigned long long*)&seed[j], (unsigned long long)v);
+}
+
 }  // namespace sr

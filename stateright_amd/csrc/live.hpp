@@ -111,6 +111,35 @@
 // (LIVE_PLAN_HOME). There is no NOTME segment. The walk takes every slot that C enables anywhere, so it is
 // strongly fair on its own states (live_loop_strong_fair); end_kind 2, loop_start = stem_len.
 //
+// LEADS-TO (a property kind of its own: `expectation(p) == LEADS_TO`, models.hpp has_lmask; TLA+'s P ~> Q, and
+// []<>Q where the trigger is true). `discovers(p, .)` is the TARGET condition Q, `leads_from(p, .)` the TRIGGER
+// P. For a leads-to property p in mode m (any of the four above):
+//   X_Q        the mode's set for the condition Q, exactly as defined above: F_p, F_p' or FairF, the reachable
+//              states from which a (fair) maximal run exists on which Q never holds. X_Q is a subset of N_p, so
+//              a state where Q holds is never in it;
+//   triggered  |{ s in R : P(s) }|;   pending  |{ s in R : P(s) and not Q(s) }|;
+//   violating  |{ s in R : P(s) and s in X_Q }| (a state counts once, however many runs from it avoid Q).
+// p has a counterexample iff violating > 0; triggered == 0 is reported as vacuous. Where `eventually` asks
+// "is some INIT state in X_Q", leads-to asks "is some REACHABLE state where P holds in X_Q": everything
+// before that question (mark, trim, components, ranks) is the `eventually` pass unchanged.
+//   SEED      depth(s) is the breadth-first distance of s from the init states (its level in the search). The
+//             seed is the violating state of lowest depth, among those the lowest compared word by word from
+//             word 0, unsigned (live_leads_less). Never the arena index: in FAST order it differs from run to
+//             run, and the seed must not.
+//   WITNESS   prefix ++ suffix. The suffix is the mode's witness above started at the seed in place of an
+//             init state (live_walk, or the stem and the closed walk). The prefix is the search's own tree
+//             path from an init state to the seed: depth(seed) steps; Q may hold on it; the unique reference-
+//             order path in FIFO order, some shortest path in FAST order. trigger_index = depth(seed) is the
+//             seed's index on the path; loop_start is an index into the whole path and >= trigger_index; a
+//             fair mode's stem_len counts from the seed. init_index is the lowest index of an init state
+//             equal to the path's first state.
+//   ACCEPTANCE  (host, Engine::live_accept / live_accept_loop / live_replay with the offset trigger_index):
+//             every step of the whole path is a successor in `actions()` order; P holds at trigger_index; Q
+//             holds on no state from trigger_index on; the terminal, stutter-end, loop-equality and loop-
+//             fairness checks apply to the suffix; a loop that closes on a prefix state is an engine error.
+// One seed only: the other violating states are counted, not witnessed. The witness is not the shortest
+// beyond its prefix.
+//
 // The per-state rule and the witness step are ONE function, live_step below, which the kernels
 // (kernels_live.hpp: live_trim, live_walk) and the host form (live_host, the sr_liveness_host entry
 // point) instantiate; they differ only in how "is this successor in the set" is answered (the alive
@@ -149,6 +178,35 @@ SR_HD bool live_same(const u64* a, const u64* b) {
 #pragma unroll
     for (int i = 0; i < W; ++i) eq = eq && a[i] == b[i];
     return eq;
+}
+
+// ---- leads-to: the rule's per-state pieces, shared by the kernels (live_leads_scan, live_leads_min) and the
+// host form (LiveLeadsStart) ----
+
+// The trigger of property p at s (false for a model without leads-to properties).
+template <class M>
+SR_HD bool live_leads_from(const M& m, int p, const u64* s) {
+    if constexpr (has_lmask<M>::value) return m.leads_from(p, s);
+    else return false;
+}
+
+// What a state adds to the three counts: bit 0 triggered, bit 1 pending, bit 2 violating. in_x: s is in X_Q.
+enum LiveLeadsBits : u32 { LIVE_LEADS_TRIGGERED = 1, LIVE_LEADS_PENDING = 2, LIVE_LEADS_VIOLATING = 4 };
+template <class M, class InX>
+SR_HD u32 live_leads_class(const M& m, int p, const u64* s, InX&& in_x) {
+    if (!live_leads_from(m, p, s)) return 0;
+    if (!live_not_p(m, p, s)) return LIVE_LEADS_TRIGGERED;
+    return LIVE_LEADS_TRIGGERED | LIVE_LEADS_PENDING | (in_x() ? (u32)LIVE_LEADS_VIOLATING : 0u);
+}
+
+// The seed's tie-break among violating states of one depth: a before b iff a is lower word by word from
+// word 0, unsigned.
+template <int W>
+SR_HD bool live_leads_less(const u64* a, const u64* b) {
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+        if (a[i] != b[i]) return a[i] < b[i];
+    return false;
 }
 
 // Whether the model's own hook names its self-loops exactly (2pc: `enabled_moves` leaves the slots
@@ -371,7 +429,8 @@ struct LiveHostFair {
 };
 
 // The reachable set: a search over at most max_states states, which numbers them in the order it finds
-// them. Refuses a p that is no `eventually` property.
+// them. Refuses a p that is no `eventually` property (leads: no leads-to property). tree() gives every
+// state's depth and its parent in the reference's FIFO order, for the prefix of a leads-to witness.
 template <class M>
 struct LiveHostSet {
     static constexpr int W = M::W;
@@ -388,9 +447,9 @@ struct LiveHostSet {
     std::vector<std::vector<u64>> st;
     std::vector<u32> init_idx;  // the init states' numbers, in the order of `init_states`
 
-    LiveHostSet(const M& m_, int p, u64 max_states_) : m(m_), max_states(max_states_) {
-        if (p < 0 || p >= M::NPROPS || m.expectation(p) != EVENTUALLY)
-            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + " is not an `eventually` property");
+    LiveHostSet(const M& m_, int p, u64 max_states_, bool leads = false) : m(m_), max_states(max_states_) {
+        if (p < 0 || p >= M::NPROPS || m.expectation(p) != (leads ? LEADS_TO : EVENTUALLY))
+            throw Error(SR_ERR_ARG, "liveness: property " + std::to_string(p) + (leads ? " is not a leads-to property" : " is not an `eventually` property"));
         const std::vector<u64> inits = init_states_of(m);
         for (size_t i = 0; i < inits.size() / W; ++i) init_idx.push_back(add(&inits[i * W]));
         for (size_t q = 0; q < st.size(); ++q) {
@@ -414,7 +473,94 @@ struct LiveHostSet {
         if (it == index.end()) throw Error(SR_ERR_NONDETERMINISM, "liveness: a successor of a reachable state is not in the reachable set");
         return it->second;
     }
+    // The search tree of the reference's single-threaded FIFO order (bfs.rs: pop_back / push_front): level 0 is
+    // popped in REVERSE init order, a popped state's successors are queued in `actions()` order, and the first
+    // state to generate t is its parent. depth[t] is t's breadth-first distance; parent ~0 for level 0.
+    void tree(std::vector<u32>& depth, std::vector<u32>& parent) const {
+        depth.assign(st.size(), ~0u);
+        parent.assign(st.size(), ~0u);
+        std::vector<u32> q;
+        for (size_t i = init_idx.size(); i-- > 0;)
+            if (depth[init_idx[i]] == ~0u) depth[init_idx[i]] = 0, q.push_back(init_idx[i]);
+        for (size_t head = 0; head < q.size(); ++head) {
+            const u32 v = q[head];
+            for_each_successor(m, st[v].data(), [&](int, const u64* ns) {
+                const u32 t = find(ns);
+                if (depth[t] == ~0u) depth[t] = depth[v] + 1, parent[t] = v, q.push_back(t);
+            });
+        }
+    }
 };
+
+// Where a host form's witness starts: start(R, in, h) returns the number of its first state in R (~0: there is
+// none, the property holds), having put what precedes that state (nothing, or a leads-to prefix: its states
+// but the last, and its actions) into h.words and h.actions and set h.r.init_index; in(i) says whether state
+// i is in the mode's set X. The default: the init state of lowest index in X.
+struct LiveInitStart {
+    static constexpr bool leads = false;
+    template <class M, class In>
+    u32 operator()(const LiveHostSet<M>& R, In&& in, LiveHost& h) const {
+        for (size_t i = 0; i < R.init_idx.size(); ++i)
+            if (in(R.init_idx[i])) {
+                h.r.init_index = (int32_t)i;
+                return R.init_idx[i];
+            }
+        return ~0u;
+    }
+};
+
+// The start of a leads-to property's witness (the header's LEADS-TO rule): the three counts over R, the seed,
+// and the FIFO tree path to it as the prefix.
+struct LiveLeadsStart {
+    static constexpr bool leads = true;
+    int p;
+    sr_live_leads& L;
+    template <class M, class In>
+    u32 operator()(const LiveHostSet<M>& R, In&& in, LiveHost& h) const {
+        constexpr int W = M::W;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<u32> depth, parent;
+        R.tree(depth, parent);
+        u32 seed = ~0u;
+        for (u32 i = 0; i < (u32)R.st.size(); ++i) {
+            const u32 c = live_leads_class(R.m, p, R.st[i].data(), [&] { return in(i); });
+            L.triggered += c & LIVE_LEADS_TRIGGERED ? 1 : 0;
+            L.pending += c & LIVE_LEADS_PENDING ? 1 : 0;
+            if (!(c & LIVE_LEADS_VIOLATING)) continue;
+            L.violating += 1;
+            if (seed == ~0u || depth[i] < depth[seed] || (depth[i] == depth[seed] && live_leads_less<W>(R.st[i].data(), R.st[seed].data())))
+                seed = i;
+        }
+        L.ran = 1;
+        if (seed != ~0u) {
+            std::vector<u32> chain;
+            for (u32 v = seed; v != ~0u; v = parent[v]) chain.push_back(v);
+            std::reverse(chain.begin(), chain.end());
+            for (size_t i = 0; i < R.init_idx.size() && h.r.init_index < 0; ++i)
+                if (R.init_idx[i] == chain[0]) h.r.init_index = (int32_t)i;
+            for (size_t k = 0; k + 1 < chain.size(); ++k) {
+                const std::vector<u64>& s = R.st[chain[k]];
+                h.words.insert(h.words.end(), s.begin(), s.end());
+                i64 id = -1;
+                for_each_successor(R.m, s.data(), [&](int a, const u64* ns) {
+                    if (id < 0 && std::equal(ns, ns + W, R.st[chain[k + 1]].data())) id = R.m.action_id(s.data(), a);
+                });
+                if (id < 0) throw Error(SR_ERR_NONDETERMINISM, "liveness: a tree edge of the prefix is no step of the model");
+                h.actions.push_back(id);
+            }
+            L.trigger_index = L.trigger_depth = (int64_t)chain.size() - 1;
+        }
+        L.seed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return seed;
+    }
+};
+
+inline sr_live_leads live_leads_none() {
+    sr_live_leads l;
+    std::memset(&l, 0, sizeof(l));
+    l.trigger_index = l.trigger_depth = -1;
+    return l;
+}
 
 // The fixpoint over R (in place, worklist by worklist as the device runs it): fills r's counters and returns
 // the alive vector, F_p (FAIR: F_p'). FAIR: progress fairness; MOVES: see live_step.
@@ -444,24 +590,23 @@ std::vector<char> live_host_fixpoint(const LiveHostSet<M>& R, int p, sr_live_res
     return alive;
 }
 
-// The plain and the progress form: the reachable set, the fixpoint and the witness.
-template <bool FAIR = false, bool MOVES = true, class M>
-LiveHost live_host(const M& m, int p, u64 max_states) {
+// The plain and the progress form: the reachable set, the fixpoint and the witness from where `start` says
+// (LiveInitStart: an `eventually` property; LiveLeadsStart: a leads-to property, behind its prefix).
+template <bool FAIR = false, bool MOVES = true, class M, class Start = LiveInitStart>
+LiveHost live_host(const M& m, int p, u64 max_states, const Start& start = Start{}) {
     constexpr int W = M::W;
     const auto t0 = std::chrono::steady_clock::now();
-    const LiveHostSet<M> R(m, p, max_states);
+    const LiveHostSet<M> R(m, p, max_states, Start::leads);
     LiveHost h;
     h.unique = R.st.size();
     h.r.ran = 1;
     const std::vector<char> alive = live_host_fixpoint<FAIR, MOVES>(R, p, h.r);
-    for (size_t i = 0; i < R.init_idx.size() && h.r.init_index < 0; ++i)
-        if (alive[R.init_idx[i]]) h.r.init_index = (int32_t)i;
-    if (h.r.init_index >= 0) {
+    u32 cur = start(R, [&](u32 i) { return alive[i] != 0; }, h);
+    if (cur != ~0u) {
         auto is_alive = [&](const u64* ns) { return alive[R.find(ns)] != 0; };
-        std::unordered_map<u32, i64> at;  // state -> its position on the path
-        u32 cur = R.init_idx[h.r.init_index];
+        std::unordered_map<u32, i64> at;  // state -> its position on the path (from the start on)
         u64 out[W];
-        for (i64 t = 0;; ++t) {
+        for (i64 t = (i64)h.actions.size();; ++t) {
             h.words.insert(h.words.end(), R.st[cur].begin(), R.st[cur].end());
             auto seen = at.find(cur);
             if (seen != at.end()) {
@@ -636,9 +781,11 @@ struct LiveStrongWalk {
 // then the sink ending, or the closed walk inside g's component: per slot the plan, the target set (NOTME: the
 // members with !me(., a); TAKE: those whose a-step stays inside), ranks towards it inside the component, the
 // walk; then home to g.
-template <class Walk, bool MOVES, class M, class Stats>
+// The witness starts where `start` says (LiveInitStart, or LiveLeadsStart behind its prefix of `off` steps: stem_len
+// counts from there, loop_start is an index into the whole path).
+template <class Walk, bool MOVES, class M, class Stats, class Start>
 void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<u32>& node, const std::vector<std::vector<u32>>& members,
-                            const std::vector<u64>& masks, LiveHost& h, Stats& s) {
+                            const std::vector<u64>& masks, LiveHost& h, Stats& s, const Start& start) {
     constexpr int W = M::W, MW = M::MW;
     constexpr u32 NONE = ~0u;
     const M& m = G.R.m;
@@ -648,13 +795,12 @@ void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<
     s.goal_states = goal.size();
     s.reach_rounds += G.ranks_to(goal, [](u32) { return true; }, rank);
     for (u32 v = 0; v < G.nf; ++v) s.fair_states += rank[v] != NONE;
-    const std::vector<u32>& init_idx = G.R.init_idx;
-    for (size_t i = 0; i < init_idx.size() && h.r.init_index < 0; ++i)
-        if (G.pos[init_idx[i]] != NONE && rank[G.pos[init_idx[i]]] != NONE) h.r.init_index = (int32_t)i;
-    if (h.r.init_index < 0) return;
+    const u32 first = start(G.R, [&](u32 i) { return G.pos[i] != NONE && rank[G.pos[i]] != NONE; }, h);
+    if (first == NONE) return;
+    const int64_t off = (int64_t)h.actions.size();
     u64 notme[MW] = {}, taken[MW] = {}, mk[MW], nx[W];
-    u32 cur = G.pos[init_idx[h.r.init_index]];
-    h.words.assign(G.state(cur), G.state(cur) + W);
+    u32 cur = G.pos[first];
+    h.words.insert(h.words.end(), G.state(cur), G.state(cur) + W);
     auto step_to = [&](int a, bool loop) {  // the step by slot a, whose successor is in nx
         h.actions.push_back(m.action_id(G.state(cur), a));
         if (loop) taken[a >> 6] |= 1ull << (a & 63);
@@ -693,7 +839,7 @@ void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<
         }
     };
     walk(rank, -1, false);
-    s.stem_len = (int64_t)h.actions.size();
+    s.stem_len = (int64_t)h.actions.size() - off;
     const u32 g = cur;
     if (G.sink[g]) {
         u64 all = 0;
@@ -725,9 +871,9 @@ void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<
         targets.assign(1, g);
         segment(-1);
         h.r.end_kind = SR_LIVE_END_LOOP;
-        h.r.loop_start = s.stem_len;
-        s.loop_len = (int64_t)h.actions.size() - s.stem_len;
-        if (!Walk::loop_fair(m, &h.words[(size_t)s.stem_len * W], (size_t)s.loop_len))
+        h.r.loop_start = off + s.stem_len;
+        s.loop_len = (int64_t)h.actions.size() - off - s.stem_len;
+        if (!Walk::loop_fair(m, &h.words[(size_t)(off + s.stem_len) * W], (size_t)s.loop_len))
             throw Error(SR_ERR_NONDETERMINISM, std::string("liveness: the closed walk of the witness is not ") + Walk::FAIR + " fair");
     }
     h.r.witness_len = (int64_t)h.actions.size();
@@ -735,13 +881,13 @@ void live_host_fair_witness(const LiveHostGraph<MOVES, M>& G, const std::vector<
 
 // A fair form: the host search and the progress fixpoint as live_host<true> runs them, G' and |U|, the mode's
 // decomposition (decompose(G, s, node, members, masks): see live_host_fair_witness), the witness, the times.
-template <class Walk, class Stats, bool MOVES, class M, class Decompose>
-LiveHostFair<Stats> live_host_fair(const M& m, int p, u64 max_states, Decompose&& decompose) {
+template <class Walk, class Stats, bool MOVES, class M, class Decompose, class Start>
+LiveHostFair<Stats> live_host_fair(const M& m, int p, u64 max_states, Decompose&& decompose, const Start& start) {
     if constexpr (!fair_slots_model<M>) {
         throw Error(SR_ERR_UNSUPPORTED, std::string(Walk::NAME) + ": this model's slots are not fairness classes");
     } else {
         const auto t0 = std::chrono::steady_clock::now();
-        const LiveHostSet<M> R(m, p, max_states);
+        const LiveHostSet<M> R(m, p, max_states, Start::leads);
         LiveHostFair<Stats> res;
         res.h.unique = R.st.size();
         res.h.r.ran = res.s.ran = 1;
@@ -753,7 +899,7 @@ LiveHostFair<Stats> live_host_fair(const M& m, int p, u64 max_states, Decompose&
         std::vector<std::vector<u32>> members;
         std::vector<u64> masks;
         decompose(G, res.s, node, members, masks);
-        live_host_fair_witness<Walk>(G, node, members, masks, res.h, res.s);
+        live_host_fair_witness<Walk>(G, node, members, masks, res.h, res.s, start);
         const auto t2 = std::chrono::steady_clock::now();
         res.h.r.pass_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
         res.s.pass_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -763,8 +909,8 @@ LiveHostFair<Stats> live_host_fair(const M& m, int p, u64 max_states, Decompose&
 
 // WEAK FAIRNESS on the host: the maximal components of G' (one Tarjan over everything), their and_me and
 // or_took accumulators and live_fair_masks; the fair ones are the witness' components.
-template <bool MOVES = true, class M>
-LiveHostFair<sr_live_weak> live_host_weak(const M& m, int p, u64 max_states) {
+template <bool MOVES = true, class M, class Start = LiveInitStart>
+LiveHostFair<sr_live_weak> live_host_weak(const M& m, int p, u64 max_states, const Start& start = Start{}) {
     return live_host_fair<LiveWeakWalk, sr_live_weak, MOVES>(
         m, p, max_states, [](auto& G, sr_live_weak& wk, std::vector<u32>& node, std::vector<std::vector<u32>>& members, std::vector<u64>& and_me) {
             constexpr int MW = M::MW;
@@ -791,14 +937,14 @@ LiveHostFair<sr_live_weak> live_host_weak(const M& m, int p, u64 max_states) {
             }
             for (u32 v = 0; v < G.nf; ++v)
                 if (comp[v] != NONE && fair[comp[v]]) node[v] = comp[v];
-        });
+        }, start);
 }
 
 // STRONG FAIRNESS on the host: the decomposition tree component by component. A job is a vertex set X and its
 // depth; in_x[v] == the job's number while it runs. Tarjan yields the components of G'[X]; a fair node keeps
 // its number in node[v] and its or_me mask, an unfair one puts X' on the stack.
-template <bool MOVES = true, class M>
-LiveHostFair<sr_live_strong> live_host_strong(const M& m, int p, u64 max_states) {
+template <bool MOVES = true, class M, class Start = LiveInitStart>
+LiveHostFair<sr_live_strong> live_host_strong(const M& m, int p, u64 max_states, const Start& start = Start{}) {
     return live_host_fair<LiveStrongWalk, sr_live_strong, MOVES>(
         m, p, max_states, [](auto& G, sr_live_strong& sg, std::vector<u32>& node, std::vector<std::vector<u32>>& members, std::vector<u64>& node_or_me) {
             constexpr int MW = M::MW;
@@ -844,7 +990,7 @@ LiveHostFair<sr_live_strong> live_host_strong(const M& m, int p, u64 max_states)
                     if (sub.x.size() >= 2) jobs.push_back(std::move(sub));
                 });
             }
-        });
+        }, start);
 }
 
 }  // namespace sr

@@ -26,7 +26,7 @@ using i64 = int64_t;
 
 #define SR_HD __host__ __device__ __forceinline__
 
-enum Expect { ALWAYS = 0, EVENTUALLY = 1, SOMETIMES = 2 };
+enum Expect { ALWAYS = 0, EVENTUALLY = 1, SOMETIMES = 2, LEADS_TO = 3 };
 
 // Mask of a model's `eventually` properties (0 for models without an `emask()` member).
 template <class M, class = void>
@@ -36,6 +36,21 @@ struct has_emask<M, std::void_t<decltype(std::declval<const M&>().emask())>> : s
 template <class M>
 inline u32 model_emask(const M& m) {
     if constexpr (has_emask<M>::value) return m.emask();
+    else return 0;
+}
+
+// Mask of a model's leads-to properties (0 for models without an `lmask()` member). Such a property p
+// (`expectation(p) == LEADS_TO`) has `discovers(p, s)` as its TARGET condition Q, the role it has for
+// `eventually`, and `leads_from(p, s)` as its TRIGGER P: "whenever P, eventually Q" (live.hpp, LEADS-TO).
+// The search never evaluates it: its bit is in no `undiscovered` mask handed to a kernel and not in
+// emask(); only the complete liveness check decides it.
+template <class M, class = void>
+struct has_lmask : std::false_type {};
+template <class M>
+struct has_lmask<M, std::void_t<decltype(std::declval<const M&>().lmask())>> : std::true_type {};
+template <class M>
+inline u32 model_lmask(const M& m) {
+    if constexpr (has_lmask<M>::value) return m.lmask();
     else return 0;
 }
 
@@ -1046,6 +1061,28 @@ struct LiveGraphT {
 using LiveGraph = LiveGraphT<1>;
 
 // -----------------------------------------------------------------------------------------------
+// LeadsGraph(n_bits, degree, seed, p_mod, t_mod, roots, q_mod[, words[, dup]]): LiveGraph's graph, key
+// and description, with the leads-to properties of the complete check (live.hpp, LEADS-TO):
+//   0  eventually "marked", as in LiveGraph;
+//   1  leads-to "armed ~> marked": the trigger is q_mod > 0 and r(v, degree + 2) % q_mod == 0;
+//   2  leads-to "always eventually marked": the trigger is true ([]<>marked).
+// -----------------------------------------------------------------------------------------------
+template <int W_>
+struct LeadsGraphT : LiveGraphT<W_> {
+    using B = LiveGraphT<W_>;
+    static constexpr int NPROPS = 3;
+    u32 q_mod = 0;
+    u32 emask() const { return 1u; }
+    SR_HD u32 lmask() const { return 6u; }
+    SR_HD bool leads_from(int p, const u64* s) const {
+        return p == 2 || (p == 1 && q_mod && B::r(s[0], (u64)B::degree + 2) % q_mod == 0);
+    }
+    int expectation(int p) const { return p == 0 ? EVENTUALLY : LEADS_TO; }
+    const char* prop_name(int p) const { return p == 0 ? "marked" : p == 1 ? "armed ~> marked" : "always eventually marked"; }
+};
+using LeadsGraph = LeadsGraphT<1>;
+
+// -----------------------------------------------------------------------------------------------
 // SpinLock(n): n threads take a lock in turn while a clock ticks (no reference counterpart; the
 // model of the complete `eventually` check's weak-fairness mode, live.hpp). One word, and the
 // packed key is the word. The key is DECLARED 8 bits wider than the word, as LiveGraph's is: (n + 1)
@@ -1107,6 +1144,81 @@ struct SpinLock {
     std::string action_name(i64 id) const {
         if (id == 2 * n) return "Tick";
         return std::string(id < n ? "Acquire(" : "Release(") + std::to_string(id < n ? id : id - n) + ")";
+    }
+};
+
+// -----------------------------------------------------------------------------------------------
+// ReqLock(n): SpinLock's lock with threads that first have to ASK for it (no reference counterpart; the
+// model of the leads-to check, live.hpp LEADS-TO). One word, the packed key is the word, declared 8 bits
+// wider as SpinLock's is. N threads (1..8) is a template parameter: the model has N + 1 properties.
+//   [0,5)      holder   0 = free, i + 1 = thread i holds the lock
+//   [5,5+n)    waiting  bit i: thread i has asked and does not hold yet
+//   5+n        tick
+// Slot i < n is Request(i), enabled iff thread i neither waits nor holds: it sets waiting(i); n + i is
+// Acquire(i), enabled iff the lock is free and i waits: i holds, waiting(i) is cleared; 2n + i is Release(i),
+// enabled iff i holds: the lock is free again; 3n is Tick, always enabled, flipping tick. No slot is a no-op
+// and a slot is a fairness class. (2^n + n 2^(n-1)) 2 states, one init state (all zero).
+//   p < n  leads-to "thread p waiting ~> thread p holds": refuted with no fairness and under progress fairness
+//          by the clock's cycle, under weak fairness for n >= 2 by starvation (Acquire(p) is disabled whenever
+//          another thread holds), proved under strong fairness
+//   n      eventually "some thread holds": refuted with no and under progress fairness, holds under weak
+// -----------------------------------------------------------------------------------------------
+template <int N>
+struct ReqLockT {
+    static_assert(N >= 1 && N <= 8, "ReqLock: 1..8 threads");
+    static constexpr int W = 1, MW = 1, NPROPS = N + 1;
+    static constexpr bool FAIR_SLOTS = true;
+    static constexpr bool SELF_LOOPS_EXACT = true;  // every enabled slot changes the state
+    static constexpr int n = N;
+    int max_actions() const { return 3 * n + 1; }
+    int max_out_degree() const { return n + 1; }
+    u32 emask() const { return 1u << n; }
+    SR_HD u32 lmask() const { return (1u << n) - 1; }
+    SR_HD void enabled(const u64* sp, u64* m) const {
+        const u32 holder = (u32)(sp[0] & 31);
+        const u64 all = (1ull << n) - 1, waiting = sp[0] >> 5 & all;
+        u64 e = 1ull << (3 * n);
+        if (holder) e |= (~waiting & all & ~(1ull << (holder - 1))) | 1ull << (2 * n + holder - 1);
+        else e |= (~waiting & all) | waiting << n;
+        m[0] = e;
+    }
+    SR_HD bool apply(const u64* sp, int a, u64* o) const {
+        const u64 s = sp[0];
+        if (a < n) o[0] = s | 1ull << (5 + a);                                          // Request
+        else if (a < 2 * n) o[0] = (s & ~(1ull << (5 + a - n))) | (u64)(a - n + 1);     // Acquire (enabled: holder == 0)
+        else if (a < 3 * n) o[0] = s & ~31ull;                                          // Release
+        else o[0] = s ^ 1ull << (5 + n);
+        return true;
+    }
+    SR_HD bool discovers(int p, const u64* sp) const {  // the condition holds
+        const u32 holder = (u32)(sp[0] & 31);
+        return p < n ? holder == (u32)p + 1 : holder != 0;
+    }
+    SR_HD bool leads_from(int p, const u64* sp) const { return p < n && (sp[0] >> (5 + p) & 1); }
+    int init_states(u64* out) const { out[0] = 0; return 1; }
+    int expectation(int p) const { return p < n ? LEADS_TO : EVENTUALLY; }
+    const char* prop_name(int p) const {
+        static const char* const names[8] = {
+            "thread 0 waiting ~> thread 0 holds", "thread 1 waiting ~> thread 1 holds", "thread 2 waiting ~> thread 2 holds",
+            "thread 3 waiting ~> thread 3 holds", "thread 4 waiting ~> thread 4 holds", "thread 5 waiting ~> thread 5 holds",
+            "thread 6 waiting ~> thread 6 holds", "thread 7 waiting ~> thread 7 holds"};
+        return p < n ? names[p] : "some thread holds";
+    }
+    int qkey_bits() const { return 14 + n; }
+    SR_HD unsigned __int128 qkey(const u64* s) const { return s[0]; }
+    int describe_width() const { return 3; }
+    void describe(const u64* s, i64* d) const {
+        d[0] = (i64)(s[0] & 31);
+        d[1] = (i64)(s[0] >> 5 & ((1ull << n) - 1));
+        d[2] = (i64)(s[0] >> (5 + n) & 1);
+    }
+    void undescribe(const i64* d, u64* s) const { s[0] = ((u64)d[0] & 31) | ((u64)d[1] & ((1ull << n) - 1)) << 5 | ((u64)d[2] & 1) << (5 + n); }
+    i64 action_id(const u64*, int a) const { return a; }
+    i64 action_id_bound() const { return 3 * n + 1; }
+    std::string action_name(i64 id) const {
+        if (id == 3 * n) return "Tick";
+        const char* kind = id < n ? "Request(" : id < 2 * n ? "Acquire(" : "Release(";
+        return std::string(kind) + std::to_string(id % n) + ")";
     }
 };
 

@@ -57,6 +57,9 @@ std::unique_ptr<EngineBase> reg_spread(const EngineArgs& a);          // the Spr
 std::unique_ptr<EngineBase> reg_two_phase_live(const EngineArgs& a);  // 2pc with `eventually` properties (TwoPhaseLive)
 std::unique_ptr<EngineBase> reg_spin_lock(const EngineArgs& a);       // SpinLock
 std::unique_ptr<EngineBase> reg_fair_rings(const EngineArgs& a);      // FairRings
+std::unique_ptr<EngineBase> reg_leads(const EngineArgs& a);           // LeadsGraph (W = 1, 2, 4), LeadsDGraph
+std::unique_ptr<EngineBase> reg_req_lock(const EngineArgs& a);        // ReqLock, 1..4 threads
+std::unique_ptr<EngineBase> reg_req_lock_wide(const EngineArgs& a);   // ReqLock, 5..8 threads
 
 // SpinLock (models.hpp) of (threads), handed to f: the engine (reg_spin_lock.hip) and the host-only entry
 // points (engine.hip) validate alike.
@@ -106,6 +109,47 @@ auto with_live_graph(const i64* p, int np, F&& f) {
     if (w == 1) return f(LiveGraphT<1>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
     if (w == 2) return f(LiveGraphT<2>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
     return f(LiveGraphT<4>{(int)p[0], (int)p[1], (u64)p[2], (u32)p[3], (u32)p[4], (int)p[5], (int)dup});
+}
+
+// The LeadsGraph fixture (models.hpp) of (n_bits, degree, seed, p_mod, t_mod, roots, q_mod) and optionally words
+// and dup: LiveGraph's parameters with q_mod behind roots, handed to f.
+template <class F>
+auto with_leads_graph(const i64* p, int np, F&& f) {
+    if (np < 7 || np > 9)
+        throw Error(SR_ERR_ARG, "leads graph needs 7 params (n_bits, degree, seed, p_mod, t_mod, roots, q_mod) and optionally words, dup");
+    if (p[6] < 0 || p[6] > 0xffffffffll) throw Error(SR_ERR_ARG, "leads graph: q_mod must be in 0..2^32-1");
+    i64 lp[8] = {p[0], p[1], p[2], p[3], p[4], p[5], np > 7 ? p[7] : 1, np > 8 ? p[8] : 0};
+    return with_live_graph(lp, 8, [&](const auto& g) {
+        constexpr int GW = std::decay_t<decltype(g)>::W;
+        LeadsGraphT<GW> m;
+        static_cast<LiveGraphT<GW>&>(m) = g;
+        m.q_mod = (u32)p[6];
+        return f(m);
+    });
+}
+
+// ReqLock (models.hpp) of (threads), handed to f as ReqLockT<threads>: the engines (reg_req_lock.hip for LO = 1,
+// threads 1..4; reg_req_lock_wide.hip for LO = 5, threads 5..8: two units, since every thread count is a model
+// of its own) and the host-only entry points (engine.hip, both ranges) validate alike.
+inline void req_lock_threads(const i64* p, int np) {
+    if (np < 1) throw Error(SR_ERR_ARG, "req-lock needs 1 param (threads)");
+    if (p[0] < 1 || p[0] > 8) throw Error(SR_ERR_UNSUPPORTED, "req-lock: threads must be in 1..=8");
+}
+template <int LO, class F>
+auto with_req_lock_range(const i64* p, int np, F&& f) {
+    req_lock_threads(p, np);
+    switch (p[0] - LO) {
+        case 0: return f(ReqLockT<LO>{});
+        case 1: return f(ReqLockT<LO + 1>{});
+        case 2: return f(ReqLockT<LO + 2>{});
+        case 3: return f(ReqLockT<LO + 3>{});
+    }
+    throw Error(SR_ERR_ARG, "req-lock: threads outside this unit's range");
+}
+template <class F>
+auto with_req_lock(const i64* p, int np, F&& f) {
+    req_lock_threads(p, np);
+    return p[0] <= 4 ? with_req_lock_range<1>(p, np, f) : with_req_lock_range<5>(p, np, f);
 }
 
 // The Spread fixture (models.hpp) of the parameters (words, key_bits, free_bits, loops, mark) and

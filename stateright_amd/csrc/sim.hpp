@@ -213,11 +213,13 @@ struct SimFpGiven {
 template <class M, class Hit, class Step, class Loops, class Fp = SimFpOwn>
 SR_HD u32 sim_advance(const M& m, SimWalk<M>& wk, u32 max_depth, u32 emask, Hit&& on_hit, Step&& on_step, Loops& lp,
                       const Fp& fpv = Fp{}) {
+    u32 skip = 0;  // leads-to properties (models.hpp has_lmask) are left unchecked: a walk decides none
+    if constexpr (has_lmask<M>::value) skip = m.lmask();
 #pragma unroll
     for (int p = 0; p < M::NPROPS; ++p) {
         if (emask >> p & 1) {
             if (!(wk.sat >> p & 1) && m.discovers(p, wk.s)) wk.sat |= 1u << p;
-        } else if (!(wk.hit >> p & 1) && m.discovers(p, wk.s)) {
+        } else if (!((wk.hit | skip) >> p & 1) && m.discovers(p, wk.s)) {
             wk.hit |= 1u << p;
             on_hit(p, wk.t);
         }

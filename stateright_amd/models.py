@@ -282,6 +282,62 @@ class LiveGraph(_Model):
         return p if self.words == 1 else p + [self.words]
 
 
+class LeadsGraph(_Model):
+    """`LiveGraph`'s graph with the leads-to properties of the complete check (csrc/models.hpp `LeadsGraph`;
+    no reference counterpart): 0 `eventually "marked"` as there; 1 leads-to "armed ~> marked", whose trigger
+    holds at v iff q_mod > 0 and r(v, degree + 2) % q_mod == 0; 2 leads-to "always eventually marked", whose
+    trigger is true."""
+    MODEL_ID = N.SR_MODEL_LEADS_GRAPH
+
+    def __init__(self, n_bits, degree, seed, p_mod, t_mod, roots, q_mod, words=1, dup=0):
+        self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots = n_bits, degree, seed, p_mod, t_mod, roots
+        self.q_mod, self.words, self.dup = q_mod, words, dup
+
+    def params(self):
+        p = [self.n_bits, self.degree, self.seed, self.p_mod, self.t_mod, self.roots, self.q_mod]
+        if self.dup:
+            return p + [self.words, self.dup]
+        return p if self.words == 1 else p + [self.words]
+
+
+class ReqLock(_Model):
+    """A lock whose `threads` threads (1..8) first have to ask for it, while a clock ticks (csrc/models.hpp
+    `ReqLockT`; no reference counterpart): Request(i), Acquire(i) while the lock is free and i waits,
+    Release(i) by its holder, and Tick, always enabled. Property p < threads is the leads-to property
+    "thread p waiting ~> thread p holds": refuted with no fairness and under progress fairness by the clock's
+    cycle, under `weak_fairness()` for two or more threads by starvation, proved under `strong_fairness()`.
+    Property `threads` is `eventually "some thread holds"`."""
+    MODEL_ID = N.SR_MODEL_REQ_LOCK
+
+    def __init__(self, threads):
+        if not 1 <= threads <= 8:
+            raise ValueError("ReqLock: threads must be in 1..=8")
+        self.threads = threads
+
+    def params(self):
+        return [self.threads]
+
+
+class LeadsDGraph(_Model):
+    """`DGraph`'s adjacency from paths with an explicit list of trigger nodes (csrc/dgraph.hpp `LeadsDGraph`),
+    for hand-drawn graphs of at most 256 states: one leads-to property "trigger ~> odd"."""
+    MODEL_ID = N.SR_MODEL_LEADS_DGRAPH
+
+    def __init__(self, triggers=(), paths=()):
+        self.triggers = list(triggers)
+        self.paths = [list(p) for p in paths]
+
+    def with_path(self, path):
+        return LeadsDGraph(self.triggers, self.paths + [list(path)])
+
+    def params(self):
+        p = [len(self.triggers)] + self.triggers
+        for path in self.paths:
+            p.append(len(path))
+            p.extend(path)
+        return p
+
+
 class SingleCopyRegister(_Model):
     """The single-copy register `SingleCopyModelCfg { client_count, server_count }.into_model()`
     (examples/single-copy-register.rs:40-78): SingleCopyActor servers (a register value each, no
