@@ -125,8 +125,20 @@ enum sr_model_id {
                                      thread p holds"; property n: eventually "some thread holds". The model of the
                                      leads-to check: refuted with no, progress and (n >= 2) weak fairness, proved
                                      under strong fairness */
-    SR_MODEL_LEADS_DGRAPH = 21    /* (n_trig, t.., len, v.., len, v..) SR_MODEL_DGRAPH's adjacency from paths, with
+    SR_MODEL_LEADS_DGRAPH = 21,   /* (n_trig, t.., len, v.., len, v..) SR_MODEL_DGRAPH's adjacency from paths, with
                                      an explicit list of trigger nodes; one leads-to property "trigger ~> odd" */
+    SR_MODEL_STEP_GRAPH = 22,     /* (n_bits<=24, degree 1..4, seed, f_mod, t_mod, roots 1..512[, words[, dup]])
+                                     SR_MODEL_LIVE_GRAPH's graph, key and description with two STEP properties and no
+                                     other: 0 "no forbidden step", where the step (v, slot k) is forbidden iff
+                                     f_mod > 0 and r(v, degree + 3 + k) % f_mod == 0 (f_mod: any non-negative int64);
+                                     1 "never down", violated iff the successor is below v. The fixture of the step
+                                     pass */
+    SR_MODEL_2PC_STEP = 23,       /* (rm_count<=14) SR_MODEL_2PC (same states, action slots and counts) with two
+                                     STEP properties after its three: 3 "a decided RM stays decided" (holds),
+                                     4 "the TM never aborts once an RM is prepared" (refuted by RmPrepare, TmAbort) */
+    SR_MODEL_STEP_DGRAPH = 24     /* (n_pairs<=16, src, dst, .., len, v.., len, v..) SR_MODEL_DGRAPH's adjacency from
+                                     paths, with an explicit list of forbidden (src, dst) pairs; one step property
+                                     "no forbidden step" */
 };
 
 /* Visit order inside a BFS level. */
@@ -155,7 +167,9 @@ enum sr_live_end { SR_LIVE_END_NONE = 0, SR_LIVE_END_TERMINAL = 1, SR_LIVE_END_L
 /* SR_LEADS_TO has no reference counterpart: "whenever the property's trigger holds, its condition holds then
  * or later" (TLA+'s P ~> Q; always-eventually where the trigger is true). Only the complete liveness check
  * decides it (see sr_gpu_bfs_liveness_leads below); the search itself never discovers it. */
-enum sr_expectation { SR_ALWAYS = 0, SR_EVENTUALLY = 1, SR_SOMETIMES = 2, SR_LEADS_TO = 3 }; /* src/lib.rs:293-300 */
+enum sr_expectation { SR_ALWAYS = 0, SR_EVENTUALLY = 1, SR_SOMETIMES = 2, SR_LEADS_TO = 3, SR_ALWAYS_STEP = 4 }; /* src/lib.rs:293-300 */
+/* SR_ALWAYS_STEP has no reference counterpart either: an invariant over STEPS (TLA+'s [][A]_v), decided by the
+ * step pass alone (see sr_gpu_bfs_step below); the search itself never discovers it. */
 
 enum sr_status {
     SR_OK = 0,
@@ -596,6 +610,50 @@ int32_t sr_gpu_bfs_coverage_class_name(const sr_bfs* bfs, int32_t c, char* name,
 int64_t sr_coverage_host(int32_t model_id, const int64_t* params, int32_t nparams, int64_t max_states, sr_coverage* out,
                          uint64_t* enabled, uint64_t* taken, uint64_t* moved, int32_t class_cap, uint64_t* holds,
                          int32_t prop_cap, char* names, int32_t names_cap);
+
+/* ---- STEP properties (expectation SR_ALWAYS_STEP; stateright_amd/csrc/step.hpp has the definition, for host
+ * and device from one source) ----
+ * A step property is an invariant over the steps of the model: the model's `step_holds(p, s, a, t)` hook says
+ * whether the step from s through action slot a to t is allowed. An EDGE is a pair (s, a) with s a distinct
+ * reachable state, a in enabled(s) and apply(s, a) yielding a state within the boundary (the coverage pass'
+ * "taken"; a step back to s itself is an edge like any other). With no option at all, a one-GPU search that
+ * ended having explored everything is followed by one more expansion of every reachable state, on the GPU and
+ * without the visited set, that counts per step property: edges (the same for every property), violations (the
+ * edges where the hook is false) and sources (the states with a violating edge). The property has a
+ * counterexample iff violations > 0. The SEED is the violating edge whose source has the lowest depth, then the
+ * source lowest compared word by word from word 0, unsigned, then the lowest slot; the witness is the search's
+ * own tree path from an init state to the seed's source followed by the seed's action: step_index + 1 actions,
+ * the last state the seed's successor. It is the property's discovery (sr_gpu_bfs_discovery*). An undiscovered
+ * step property makes the search explore everything. ran = 0 (the property is NOT CHECKED, never refused at
+ * spawn, and the search stops as if it were absent): the partitioned spawns, symmetry, target_state_count, the
+ * simulation checker, a search that stopped early. One seed only; no early exit. */
+typedef struct sr_step_result {
+    uint32_t struct_size;  /* sizeof this struct in the caller's build (set before the call)               */
+    int32_t ran;           /* 1 = the pass ran and `prop` is a step property; with 0 the counts are 0       */
+    uint64_t edges;        /* edges of the reachable graph                                                  */
+    uint64_t violations;   /* edges on which the property does not hold                                     */
+    uint64_t sources;      /* states with at least one such edge                                            */
+    int64_t step_index;    /* index of the violating step on the witness = the seed's depth; -1 without one */
+    int64_t step_action;   /* the canonical id of the seed's action; -1 without a witness                   */
+    int32_t init_index;    /* the init state the witness starts at (the lowest index of an equal one); -1   */
+    int32_t reserved0;
+    int64_t witness_len;   /* actions of the witness = step_index + 1; -1 without one                       */
+    double scan_ms;        /* wall time of the counting launch and its read-back (shared by the properties) */
+    double min_ms;         /* wall time of this property's seed tie-break and witness                       */
+} sr_step_result;
+/* Fills *out (at most out->struct_size bytes) for property `prop` of a joined check. SR_ERR_ARG for a handle
+ * that still runs or a `prop` that is no property. */
+int32_t sr_gpu_bfs_step(const sr_bfs* bfs, int32_t prop, sr_step_result* out);
+/* Host-only: whether the LAST step of the path that the canonical action ids describe from init state `init`
+ * of a joined check's model holds for the step property `prop` (what `assert_discovery` asks): 1 it holds, 0 it
+ * violates it; -1: the actions cannot be replayed, n < 1, or `prop` is no step property. */
+int32_t sr_gpu_bfs_replay_step(const sr_bfs* bfs, int32_t init, const int64_t* action_ids, int32_t n, int32_t prop);
+/* Host-only (no device needed): the same rule by a host search of a registered model in the reference's FIFO
+ * order over at most max_states states (SR_ERR_CAPACITY beyond); the witness follows that search's tree. Writes
+ * the witness' canonical action ids (at most cap). Returns the model's unique state count, or a negative
+ * SR_ERR_*. */
+int64_t sr_step_host(int32_t model_id, const int64_t* params, int32_t nparams, int32_t prop, int64_t max_states,
+                     sr_step_result* out, int64_t* action_ids, int32_t cap);
 
 /* Host-only (no device needed): the reachable graph of a registered model, by a host search over at
  * most max_states states (SR_ERR_CAPACITY beyond), states numbered in the order the search finds

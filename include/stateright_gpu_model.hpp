@@ -29,6 +29,18 @@
  *                                             property, and it refuses plugins, so a plugin's leads-to
  *                                             properties are left unchecked by every checker (the plugin ABI
  *                                             version is unchanged); a model without lmask() has none
+ *             u32 smask()                     the mask of STEP properties (expectation(p) == ALWAYS_STEP = 4: an
+ *                                             invariant over steps, TLA+'s [][A]_v), disjoint from emask() and
+ *                                             lmask(); with it comes the hook
+ *                                             SR_HD bool step_holds(int p, const u64* s, int a, const u64* t):
+ *                                             whether the step from s through slot a to t = apply(s, a) is
+ *                                             allowed (t may equal s: the hook decides about stuttering), while
+ *                                             discovers(p, s) is false everywhere, so the search never discovers
+ *                                             it. Only the step pass decides such a property, behind a one-GPU
+ *                                             spawn_bfs / spawn_dfs that explored everything (no option;
+ *                                             stateright_amd/csrc/step.hpp); a plugin takes it like a registered
+ *                                             model (the plugin ABI version is unchanged:
+ *                                             examples/plugins/step_counter.hip); a model without smask() has none
  *             qkey_bits(), SR_HD qkey(s)      (exact quotient visited set for multi-word states)
  *             SR_HD self_loops(s, enabled, out)   out = enabled slots whose next_state is s itself:
  *                                             FAST expansion counts them (state_count) without

@@ -17,8 +17,8 @@ include/stateright_gpu.h; this package is the host-side mirror of the reference 
 from .checker import (CheckerBuilder, CheckerError, Expectation, GpuBfsChecker, GpuSimulationChecker, Path, PathRecorder,
                       StateRecorder)
 from .models import (AbdRegister, ActorFixture, BinaryClock, DGraph, FairRings, Increment, IncrementLock, LinearEquation, Paxos,
-                     PingPong, ReqLock, SingleCopyRegister, SpinLockSys, TwoPhaseLiveSys, TwoPhaseSys)
+                     PingPong, ReqLock, SingleCopyRegister, SpinLockSys, TwoPhaseLiveSys, TwoPhaseStepSys, TwoPhaseSys)
 
 __all__ = ["CheckerBuilder", "CheckerError", "Expectation", "GpuBfsChecker", "GpuSimulationChecker", "Path", "PathRecorder", "StateRecorder",
            "AbdRegister", "ActorFixture", "BinaryClock", "DGraph", "FairRings", "Increment", "IncrementLock", "LinearEquation", "Paxos",
-           "PingPong", "ReqLock", "SingleCopyRegister", "SpinLockSys", "TwoPhaseLiveSys", "TwoPhaseSys"]
+           "PingPong", "ReqLock", "SingleCopyRegister", "SpinLockSys", "TwoPhaseLiveSys", "TwoPhaseStepSys", "TwoPhaseSys"]

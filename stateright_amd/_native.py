@@ -30,9 +30,12 @@ SR_MODEL_FAIR_RINGS = 18
 SR_MODEL_LEADS_GRAPH = 19
 SR_MODEL_REQ_LOCK = 20
 SR_MODEL_LEADS_DGRAPH = 21
+SR_MODEL_STEP_GRAPH = 22
+SR_MODEL_2PC_STEP = 23
+SR_MODEL_STEP_DGRAPH = 24
 
 SR_ORDER_AUTO, SR_ORDER_FIFO, SR_ORDER_FAST = 0, 1, 2
-SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES, SR_LEADS_TO = 0, 1, 2, 3
+SR_ALWAYS, SR_EVENTUALLY, SR_SOMETIMES, SR_LEADS_TO, SR_ALWAYS_STEP = 0, 1, 2, 3, 4
 # sr_stats.root_path (enum sr_root_path)
 SR_ROOTS_INLINE, SR_ROOTS_FUSED, SR_ROOTS_LAUNCHES, SR_ROOTS_HEAD, SR_ROOTS_PARTS, SR_ROOTS_BUFFER = 1, 2, 3, 4, 5, 6
 
@@ -127,6 +130,26 @@ class sr_live_leads(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+class sr_step_result(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("ran", ctypes.c_int32),
+        ("edges", ctypes.c_uint64),
+        ("violations", ctypes.c_uint64),
+        ("sources", ctypes.c_uint64),
+        ("step_index", ctypes.c_int64),
+        ("step_action", ctypes.c_int64),
+        ("init_index", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("witness_len", ctypes.c_int64),
+        ("scan_ms", ctypes.c_double),
+        ("min_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0")}
 
 
 class sr_coverage(ctypes.Structure):
@@ -344,6 +367,10 @@ SIGNATURES = [
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
+    ("sr_gpu_bfs_step", ctypes.c_int32, [_P, ctypes.c_int32, ctypes.POINTER(sr_step_result)]),
+    ("sr_gpu_bfs_replay_step", ctypes.c_int32, [_P, ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32]),
+    ("sr_step_host", ctypes.c_int64, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                      ctypes.POINTER(sr_step_result), _I64P, ctypes.c_int32]),
     ("sr_sim_opts_init_sized", None, [ctypes.POINTER(sr_sim_opts), ctypes.c_uint32]),
     ("sr_gpu_sim_spawn", _P, [ctypes.c_int32, _I64P, ctypes.c_int32, ctypes.POINTER(sr_sim_opts)]),
     ("sr_gpu_sim_walk_records", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -655,6 +682,35 @@ def liveness_host_leads(model_id, params, prop, fairness=0, max_states=1 << 22):
     stats = sr_live_leads()
     return _liveness_host("sr_liveness_host_leads", lambda res, acts, cap: lib.sr_liveness_host_leads(
         model_id, arr, len(params), prop, mode, max_states, res, ctypes.byref(stats), acts, cap), ("leads", stats))
+
+
+def step_host(model_id, params, prop, max_states=1 << 22, struct_size=None):
+    """The step pass of a registered model on the host (sr_step_host, csrc/step.hpp; no device needed) for the
+    step property of index `prop`: the dict of sr_step_result (ran, edges, violations, sources, step_index,
+    step_action, init_index, witness_len, scan_ms, min_ms), plus `unique` (the model's reachable states) and
+    `actions` (the witness' canonical action ids; [] without one). struct_size (tests): what the caller claims
+    its struct to hold; the fields behind it keep what they had."""
+    lib = load()
+    params = list(params)
+    arr = (ctypes.c_int64 * max(1, len(params)))(*params)
+    cap = 1 << 12
+    while True:
+        res = sr_step_result()
+        if struct_size is not None:
+            ctypes.memset(ctypes.byref(res), 0xEE, ctypes.sizeof(res))
+        res.struct_size = ctypes.sizeof(res) if struct_size is None else struct_size
+        acts = (ctypes.c_int64 * cap)()
+        n = lib.sr_step_host(model_id, arr, len(params), prop, max_states, ctypes.byref(res), acts, cap)
+        if n < 0:
+            raise ValueError(f"sr_step_host: {last_error()} (status {n})")
+        if struct_size is not None or res.witness_len <= cap:
+            break
+        cap = res.witness_len
+    out = res.as_dict()
+    out["struct_size"] = res.struct_size
+    out["unique"] = n
+    out["actions"] = list(acts[:max(0, min(cap, res.witness_len))]) if struct_size is None else []
+    return out
 
 
 def runtime_versions():

@@ -17,14 +17,15 @@ SRC = os.path.join(CDIR, "engine.hip")
 UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip", "reg_increment_lock.hip",
          "reg_paxos.hip", "reg_paxos_wide.hip", "reg_ping_pong.hip", "reg_registers.hip", "reg_registers_wide.hip",
          "reg_spread.hip", "reg_two_phase_live.hip", "reg_spin_lock.hip", "reg_fair_rings.hip", "reg_leads.hip",
-         "reg_req_lock.hip", "reg_req_lock_wide.hip"]
+         "reg_req_lock.hip", "reg_req_lock_wide.hip", "reg_step.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
-                                                "dist.hpp", "dist_host.hpp", "sim.hpp", "kernels_sim.hpp", "live.hpp", "kernels_live.hpp", "cover.hpp", "kernels_cover.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
+                                                "dist.hpp", "dist_host.hpp", "sim.hpp", "kernels_sim.hpp", "live.hpp", "kernels_live.hpp", "cover.hpp", "kernels_cover.hpp", "step.hpp", "kernels_step.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
                                                 "actor.hpp", "abd_wide.hpp", "table_selftest.hpp", "kernels_audit.hpp", "rehash_selftest.hpp"]]
 HEADERS = [os.path.join(ROOT, "include", f) for f in ("stateright_gpu.h", "stateright_gpu_model.hpp")]
 OUT = os.path.join(HERE, "libstateright_gpu.so")
 OBJDIR = os.path.join(HERE, "build")
-PLUGINS = {"sliding_puzzle": os.path.join(ROOT, "examples", "plugins", "sliding_puzzle.hip")}
+PLUGINS = {"sliding_puzzle": os.path.join(ROOT, "examples", "plugins", "sliding_puzzle.hip"),
+           "step_counter": os.path.join(ROOT, "examples", "plugins", "step_counter.hip")}
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-I", os.path.join(ROOT, "include")]
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]

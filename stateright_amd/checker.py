@@ -20,6 +20,7 @@ class Expectation(enum.IntEnum):
     Sometimes = N.SR_SOMETIMES
     LeadsTo = N.SR_LEADS_TO  # (no reference counterpart: "whenever the trigger holds, eventually the condition")
     LEADS_TO = N.SR_LEADS_TO  # (an alias, under the engine's own name for it)
+    AlwaysStep = N.SR_ALWAYS_STEP  # (no reference counterpart: an invariant over steps, decided by the step pass)
 
 
 class CheckerError(RuntimeError):
@@ -730,6 +731,39 @@ class GpuBfsChecker:
     def _leads_checked(self, name):
         return bool(self._leads_info(name))
 
+    def step(self, name):
+        """The step pass' figures for the step property `name` (joins the check), a dict:
+        edges (the edges of the reachable graph: pairs of a state and an enabled action with a next state within
+        the boundary), violations (the edges on which the property does not hold), sources (the states with such
+        an edge), step_index (the index of the violating step on the discovery = the depth of its source; -1
+        without one), step_action (its canonical action id), init_index, witness_len, scan_ms, min_ms. None when
+        the property was NOT CHECKED: `name` is no step property, or the check was partitioned, ran under
+        symmetry or with a target_state_count, was a simulation, or did not explore everything."""
+        self.join()
+        res = N.sr_step_result()
+        res.struct_size = ctypes.sizeof(res)
+        st = self._lib.sr_gpu_bfs_step(self._h, self._prop_index(name), ctypes.byref(res))
+        if st != 0:
+            raise CheckerError("sr_gpu_bfs_step", st)
+        return res.as_dict() if res.ran else None
+
+    def step_index(self, name):
+        """If the step property `name` has a discovery, the index of the path's step that violates it (its last:
+        the path has step_index + 1 actions); None otherwise."""
+        s = self.step(name)
+        return s["step_index"] if s and s["step_index"] >= 0 else None
+
+    def _step_checked(self, name):
+        return self.step(name) is not None
+
+    def _last_step_holds(self, name, actions, init):
+        """The host model's answer for the last step of the path (sr_gpu_bfs_replay_step): True / False, or None
+        if the actions cannot be replayed from init state `init`."""
+        ids = [self.action_id(a) for a in actions]
+        arr = (ctypes.c_int64 * max(1, len(ids)))(*ids)
+        r = self._lib.sr_gpu_bfs_replay_step(self._h, init, arr, len(ids), self._prop_index(name))
+        return None if r < 0 else bool(r)
+
     def launch_profile(self):
         """profile(): [(kernel_ms, frontier)] of every expand launch, in launch order."""
         n = self._lib.sr_gpu_bfs_launch_profile(self._h, None, None, 0)
@@ -779,6 +813,11 @@ class GpuBfsChecker:
                 w.write(f'Leads-to "{name}": holds (triggered {ld["triggered"]} states)\n')
             else:
                 w.write(f'Leads-to "{name}": holds vacuously (never triggered)\n')
+        for name, exp in self.properties():  # a step property without a discovery: what the step pass found
+            if exp != Expectation.AlwaysStep or name in found:
+                continue
+            s = self.step(name)
+            w.write(f'Step "{name}": holds ({s["edges"]} edges)\n' if s else f'Step "{name}": not checked\n')
         return self
 
     def assert_properties(self):
@@ -804,6 +843,9 @@ class GpuBfsChecker:
         if dict(self.properties())[name] == Expectation.LeadsTo and not self._leads_checked(name):
             raise AssertionError(f'Leads-to property "{name}" was not checked (it takes complete_liveness(), '
                                  "weak_fairness() or strong_fairness(), and a search that explored everything).")
+        if dict(self.properties())[name] == Expectation.AlwaysStep and not self._step_checked(name):
+            raise AssertionError(f'Step property "{name}" was not checked (the step pass takes a spawn_bfs / spawn_dfs on '
+                                 "one GPU without symmetry or target_state_count, and a search that explored everything).")
 
     def replay(self, actions, init_index=0):
         """`Path::from_actions` on the host copy of the model: (states, conditions) or None."""
@@ -922,6 +964,12 @@ class GpuBfsChecker:
         exp = self.properties()[i][1]
         if exp == Expectation.LeadsTo:
             return self._assert_leads_discovery(name, actions, found, trigger_index, loop_start)
+        if exp == Expectation.AlwaysStep:  # any replayable path whose last step violates the property
+            held = [self._last_step_holds(name, actions, init) for init in range(self._lib.sr_gpu_bfs_init_count(self._h))]
+            if False in held:
+                return
+            why = "its last step does not violate the property" if True in held else "its actions cannot be replayed, or it has no step"
+            raise AssertionError(f'Invalid discovery for "{name}" ({why}), but a valid one was found. found={found.into_actions()}')
         loops = exp == Expectation.Eventually and self._accepts_lassos()
         info = []
         for init in range(self._lib.sr_gpu_bfs_init_count(self._h)):

@@ -165,4 +165,40 @@ struct LeadsDGraph : DGraph {
     const char* prop_name(int) const { return "trigger ~> odd"; }
 };
 
+// StepDGraph: DGraph's adjacency from paths plus an explicit list of FORBIDDEN pairs (src, dst), for hand-drawn
+// graphs of the step pass (step.hpp; no reference counterpart). One step property "no forbidden step": the step
+// from src through slot dst (the slot IS the destination) is violated iff the pair is in the list; a pair that
+// is no edge of the graph forbids nothing. Params (its own format): [n_pairs, src0, dst0, .., len0, v.., ...].
+struct StepDGraph : DGraph {
+    static constexpr int MAX_PAIRS = 16;
+    int npairs = 0;
+    u16 pairs[MAX_PAIRS] = {};  // src << 8 | dst
+
+    static StepDGraph make(const i64* p, int np, int device) {
+        if (np < 1 || p[0] < 0 || p[0] > MAX_PAIRS || 1 + 2 * p[0] > np)
+            throw Error(SR_ERR_ARG, "step dgraph: needs (n_pairs <= 16, src, dst, .., paths...)");
+        const int n = (int)p[0];
+        std::vector<i64> dp(1, (i64)ALWAYS);  // the paths, as DGraph's parameters (no `eventually` bits)
+        dp.insert(dp.end(), p + 1 + 2 * n, p + np);
+        StepDGraph m;
+        static_cast<DGraph&>(m) = DGraph::make(dp.data(), (int)dp.size(), device);
+        for (int i = 0; i < 2 * n; ++i)
+            if (p[1 + i] < 0 || p[1 + i] > 255) throw Error(SR_ERR_ARG, "step dgraph: nodes are u8");
+        m.npairs = n;
+        for (int i = 0; i < n; ++i) m.pairs[i] = (u16)(p[1 + 2 * i] << 8 | p[2 + 2 * i]);
+        return m;
+    }
+    u32 emask() const { return 0u; }
+    u32 smask() const { return 1u; }
+    SR_HD bool discovers(int, const u64*) const { return false; }
+    SR_HD bool step_holds(int, const u64* s, int a, const u64*) const {
+        const u32 key = (u32)(s[0] & 255) << 8 | (u32)(a & 255);
+        bool bad = false;
+        for (int i = 0; i < MAX_PAIRS; ++i) bad = bad || (i < npairs && pairs[i] == key);
+        return !bad;
+    }
+    int expectation(int) const { return ALWAYS_STEP; }
+    const char* prop_name(int) const { return "no forbidden step"; }
+};
+
 }  // namespace sr

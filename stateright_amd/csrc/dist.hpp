@@ -1570,7 +1570,7 @@ class DistEngine final : public EngineBase {
         gl_off_.assign(T_, 0);
         lvl0_ = 0;
         head_done_ = false;
-        head_undiscovered_ = ((1u << M::NPROPS) - 1) & ~model_lmask(m_);  // (leads-to properties are left unchecked)
+        head_undiscovered_ = ((1u << M::NPROPS) - 1) & ~model_lmask(m_) & ~model_smask(m_);  // (leads-to and step properties are left unchecked)
         const bool use_head = head_max_ > 0 && head_ok_ && T_ > 1;  // one partition: nothing to save
         const u64 per_part = hint / T_ + 1;
         stats.root_path = use_head ? SR_ROOTS_HEAD : SR_ROOTS_PARTS;
@@ -1618,7 +1618,7 @@ class DistEngine final : public EngineBase {
             SR_HIP(hipMemcpyAsync(&n0, dn.p, 4, hipMemcpyDeviceToHost, stream_));
             SR_HIP(stream_sync(stream_));
             p.n = n0;
-            if (n0) eval_roots<M><<<blocks_for(n0, 64), 64, 0, stream_>>>(m_, p.arena.p, n0, p.lc, ((1u << M::NPROPS) - 1) & ~model_lmask(m_));
+            if (n0) eval_roots<M><<<blocks_for(n0, 64), 64, 0, stream_>>>(m_, p.arena.p, n0, p.lc, ((1u << M::NPROPS) - 1) & ~model_lmask(m_) & ~model_smask(m_));
             p.seq++;
             publish_kernel<<<1, 64, 0, stream_>>>(p.lc, p.hc_dev, p.seq, 1, nullptr);
             SR_HIP(hipGetLastError());
@@ -1919,7 +1919,7 @@ class DistEngine final : public EngineBase {
         SR_HIP(hipMemsetAsync(hpar_.p, 0xff, (size_t)k * 4, stream_));
         init_counters(p0);
         insert_roots<M><<<blocks_for(k, 64), 64, 0, stream_>>>(m_, hv, harena_.p, (u32)k, p0.lc);
-        u32 und = ((1u << M::NPROPS) - 1) & ~model_lmask(m_);
+        u32 und = ((1u << M::NPROPS) - 1) & ~model_lmask(m_) & ~model_smask(m_);
         eval_roots<M><<<blocks_for(k, 64), 64, 0, stream_>>>(m_, harena_.p, (u32)k, p0.lc, und);
         p0.seq++;
         publish_kernel<<<1, 64, 0, stream_>>>(p0.lc, p0.hc_dev, p0.seq, 1, nullptr);

@@ -20,7 +20,7 @@ namespace sr {
 
 // The registry (registry.hpp): each family of models compiles in its own translation unit.
 static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
-    if (a.o->symmetry && a.model != SR_MODEL_2PC)
+    if (a.o->symmetry && a.model != SR_MODEL_2PC && a.model != SR_MODEL_2PC_STEP)
         throw Error(SR_ERR_UNSUPPORTED, "symmetry reduction: model " + std::to_string(a.model) + " has no canonical form");
     switch (a.model) {
         case SR_MODEL_LINEAR_EQUATION:
@@ -52,6 +52,10 @@ static std::unique_ptr<EngineBase> make_model_engine(const EngineArgs& a) {
         case SR_MODEL_REQ_LOCK:
             req_lock_threads(a.p, a.np);
             return a.p[0] <= 4 ? reg_req_lock(a) : reg_req_lock_wide(a);
+        case SR_MODEL_STEP_GRAPH:
+        case SR_MODEL_2PC_STEP:
+        case SR_MODEL_STEP_DGRAPH:
+            return reg_step(a);
     }
     throw Error(SR_ERR_ARG, "unknown model id " + std::to_string(a.model));
 }
@@ -469,6 +473,11 @@ static i64 with_host_model(int model, const i64* p, int np, F&& f) {
         case SR_MODEL_LEADS_DGRAPH: return f(LeadsDGraph::make(p, np, -1));  // (host tables only)
         case SR_MODEL_REQ_LOCK:
             return with_req_lock(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_STEP_GRAPH:
+            return with_step_graph(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_2PC_STEP:
+            return with_two_phase_step(p, np, [&](const auto& m) -> i64 { return f(m); });
+        case SR_MODEL_STEP_DGRAPH: return f(StepDGraph::make(p, np, -1));  // (host tables only)
         default:
             return SR_ERR_UNSUPPORTED;
     }
@@ -920,6 +929,61 @@ int64_t sr_coverage_host(int32_t model, const int64_t* p, int32_t np, int64_t ma
             return (i64)f.c.states;
         });
         if (r == SR_ERR_UNSUPPORTED) set_error("sr_coverage_host: model " + std::to_string(model) + " has no host form");
+        return r;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+// Copies a step result into the caller's mirror (at most its struct_size bytes).
+static void step_copy_out(const sr_step_result& s, sr_step_result* out) {
+    sr_step_result r = s;
+    r.struct_size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(r));
+    std::memcpy(out, &r, r.struct_size);  // only the caller's own bytes
+}
+
+int32_t sr_gpu_bfs_step(const sr_bfs* b, int32_t prop, sr_step_result* out) {
+    sr_step_result r;
+    if (!b || !out || out->struct_size < 2 * sizeof(uint32_t) || !b->e->finished.load(std::memory_order_acquire) ||
+        !b->e->step_result(prop, &r)) {
+        set_error("sr_gpu_bfs_step: a finished check, one of its properties and a sized result struct");
+        return SR_ERR_ARG;
+    }
+    step_copy_out(r, out);
+    return SR_OK;
+}
+
+int32_t sr_gpu_bfs_replay_step(const sr_bfs* b, int32_t init, const int64_t* ids, int32_t n, int32_t prop) {
+    if (!b || n < 1 || !ids) return -1;
+    try {
+        return b->e->step_replay(init, ids, n, prop);
+    } catch (const std::exception& x) {  // (the host model's replay: nothing crosses the C ABI)
+        set_error(x.what());
+        return -1;
+    }
+}
+
+int64_t sr_step_host(int32_t model, const int64_t* p, int32_t np, int32_t prop, int64_t max_states, sr_step_result* out,
+                     int64_t* action_ids, int32_t cap) {
+    try {
+        if (!out || out->struct_size < 2 * sizeof(uint32_t) || max_states < 1 || (cap > 0 && !action_ids))
+            throw Error(SR_ERR_ARG, "sr_step_host: a sized result struct, max_states >= 1 and a buffer of cap");
+        const i64 r = with_host_model(model, p, np, [&](const auto& m) -> i64 {
+            using M = std::decay_t<decltype(m)>;
+            if constexpr (!has_smask<M>::value) {
+                throw Error(SR_ERR_ARG, "step pass: the model has no step property");
+            } else {
+                const StepHost h = step_host(m, prop, (u64)max_states);
+                step_copy_out(h.r, out);
+                for (size_t i = 0; i < h.actions.size() && (int64_t)i < cap; ++i) action_ids[i] = h.actions[i];
+                return (i64)h.unique;
+            }
+        });
+        if (r == SR_ERR_UNSUPPORTED) set_error("sr_step_host: model " + std::to_string(model) + " has no host form");
         return r;
     } catch (const Error& x) {
         set_error(x.what());

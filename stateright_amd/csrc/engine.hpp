@@ -27,6 +27,7 @@
 #include "kernels_audit.hpp"
 #include "live.hpp"
 #include "cover.hpp"
+#include "step.hpp"
 
 namespace sr {
 
@@ -124,6 +125,19 @@ class EngineBase {
         return true;
     }
     CoverFigures cover;  // the coverage pass' figures (cover.hpp; c.ran = 0: it did not run)
+    std::vector<sr_step_result> step;  // per property (empty: the step pass never ran; ran = 0: no step property)
+    // The step pass' figures for property p (sr_gpu_bfs_step); false: p is no property.
+    bool step_result(int p, sr_step_result* out) const {
+        if (p < 0 || p >= nprops()) return false;
+        *out = p < (int)step.size() ? step[p] : step_none();
+        return true;
+    }
+    // Whether the last step of the path that the actions describe from init state `init` holds for the step
+    // property p (sr_gpu_bfs_replay_step): 1 / 0; -1: no such path, no step, or p is no step property.
+    virtual int step_replay(int init, const i64* ids, int n, int p) const {
+        (void)init, (void)ids, (void)n, (void)p;
+        return -1;
+    }
     std::atomic<u64> state_count{0}, unique{0};
     std::atomic<u32> max_depth{0};
     std::atomic<bool> finished{false};
@@ -429,9 +443,11 @@ class Engine final : public EngineBase {
 
   public:
     Engine(M m, const sr_opts& o)
-        : m_(m), o_(o), A_((u32)m.max_actions()), D_((u32)m.max_out_degree()), emask_(model_emask(m)), lmask_(model_lmask(m)) {
+        : m_(m), o_(o), A_((u32)m.max_actions()), D_((u32)m.max_out_degree()), emask_(model_emask(m)), lmask_(model_lmask(m)),
+          smask_(step_checked_mask(m)) {
         disc.resize(M::NPROPS);
         if (emask_ & lmask_) throw Error(SR_ERR_ARG, "a leads-to property is in the model's emask()");
+        if ((emask_ | lmask_) & smask_) throw Error(SR_ERR_ARG, "a step property is in the model's emask() or lmask()");
         (void)init_states_of(m_);  // a model with more init states than it declares fails at spawn
         if (o_.liveness) {  // the complete `eventually` check (live.hpp): what it cannot be combined with
             if (o_.target_state_count)
@@ -573,7 +589,12 @@ class Engine final : public EngineBase {
     // `Path::from_fingerprints` (src/checker/path.rs:20-86) on the host copy of the GpuModel.
     int path(int p, std::vector<i64>& actions, std::vector<i64>& states) override {
         if (p < 0 || p >= M::NPROPS || !disc[p].found) return -1;
-        if (!live_path_[p].empty()) return concrete_path(m_, live_path_[p], actions, states);
+        if (!live_path_[p].empty()) {
+            const int n = concrete_path(m_, live_path_[p], actions, states);
+            // (a step property's witness: its last action is the seed's, not the first that leads to the last state)
+            if (n > 0 && step_action_[p] >= 0) actions.back() = step_action_[p];
+            return n;
+        }
         SR_HIP(hipSetDevice(o_.device));
         std::vector<u64> st;
         tree_path(disc[p].level, disc[p].rank, st);
@@ -594,6 +615,7 @@ class Engine final : public EngineBase {
     int triggers(int init, const i64* ids, int n, int p, std::vector<int>& out) const override {
         return triggers_model(base_model(m_), init, ids, n, p, out);
     }
+    int step_replay(int init, const i64* ids, int n, int p) const override { return step_replay_model(base_model(m_), init, ids, n, p); }
     int explore(const u64* fps, int n, std::vector<i64>& action, std::vector<int>& has, std::vector<u64>& fp,
                 std::vector<i64>& states) const override {
         return explore_model(base_model(m_), fps, n, action, has, fp, states);
@@ -1061,6 +1083,8 @@ class Engine final : public EngineBase {
         live_strong.clear();
         live_leads.clear();
         live_path_.assign(M::NPROPS, {});
+        step.clear();
+        step_action_.assign(M::NPROPS, -1);
         cover = CoverFigures{};
         cover.c = cover_none();
         stats = sr_stats{};
@@ -1108,7 +1132,7 @@ class Engine final : public EngineBase {
         ensure_arena(std::max<u64>(std::max<u64>(1u << 16, arena0), (o_.capacity_hint + slack + 1024) * grow_factor_), 0);
         lstart_.assign({0, (u64)k});
         lvisited_.clear();
-        const u32 und0 = ((1u << M::NPROPS) - 1) & ~emask_ & ~lmask_;  // (no kernel of the search sees a leads-to bit)
+        const u32 und0 = ((1u << M::NPROPS) - 1) & ~emask_ & ~lmask_ & ~smask_;  // (no kernel of the search sees a leads-to or a step bit)
         u32 sq = 0;
         if ((u64)k * W <= ROOTS_INLINE_WORDS) {
             // one launch: counters reset, level 0 into the arena (no parents; `eventually` bits
@@ -1142,7 +1166,7 @@ class Engine final : public EngineBase {
         // FAST pipelined order: level 0 is enqueued before the host reads the roots' outcome (it is
         // ignored if the roots already discover every property)
         // (a model with leads-to properties takes the level loop below: its host mask differs from the kernels')
-        const bool pipelined = !fifo_ && !emask_ && !lmask_ && !o_.target_state_count && M::NPROPS > 0 && pipeline_;
+        const bool pipelined = !fifo_ && !emask_ && !lmask_ && !smask_ && !o_.target_state_count && M::NPROPS > 0 && pipeline_;
         const u32 sq_level0 = pipelined ? launch_sync((u64)k, (1u << M::NPROPS) - 1) : 0u;
         wait_publish(sq);
         state_count = (u64)k;
@@ -1151,7 +1175,11 @@ class Engine final : public EngineBase {
         // A leads-to property is decided by the liveness pass alone: with the pass on, the host keeps its bit, so
         // that the search explores everything as for an undiscovered `always`; with it off the bit is dropped and
         // the search stops as if the property were absent.
-        u32 undiscovered = ((1u << M::NPROPS) - 1) & ~(o_.liveness ? 0u : lmask_);
+        // A step property is decided by the step pass alone (step.hpp), which needs every state of a one-GPU search
+        // over concrete states: the host keeps its bit likewise, unless the check has a target_state_count or runs
+        // on orbit representatives; then the property is left unchecked.
+        const u32 step_on = o_.target_state_count || is_canon<M>::value ? 0u : smask_;
+        u32 undiscovered = ((1u << M::NPROPS) - 1) & ~(o_.liveness ? 0u : lmask_) & ~(smask_ & ~step_on);
         // A model whose properties are all leads-to, with the pass off, has nothing for the search to await: it is
         // a model without properties (below: the first pop returns, bfs.rs:226), not an early exit inside a level.
         const bool no_props = M::NPROPS == 0 || undiscovered == 0;
@@ -1253,7 +1281,7 @@ class Engine final : public EngineBase {
                 SR_HIP(stream_sync(stream_));
             }
             if (limit) {
-                produced = expand_level(level, n, limit, undiscovered & ~emask_ & ~lmask_, peb.p);
+                produced = expand_level(level, n, limit, undiscovered & ~emask_ & ~lmask_ & ~smask_, peb.p);
             } else {
                 std::memset(&lc_, 0, sizeof(lc_));
             }
@@ -1299,6 +1327,7 @@ class Engine final : public EngineBase {
         stats.table_capacity = cap_;
         if (o_.liveness && explored_all) live_pass();  // (reads the visited set: before its release)
         if (o_.coverage && (explored_all || cover_all)) cover_pass();  // (reads the arena only)
+        if (step_on && explored_all) step_pass();                     // (likewise)
         release_table();  // (the pipelined loop released it already)
         free_unzeroed_table();
         return order_dependent && !fifo_;
@@ -1498,6 +1527,22 @@ class Engine final : public EngineBase {
         keys_.reset();
     }
 
+    // Level 0 of the arena holds the init states as given, in REVERSE order: a bit mask (one bit per arena index
+    // below the init count) of the indices that repeat another init state, and how many there are.
+    static u64 repeated_inits(const std::vector<u64>& inits, std::vector<u32>& skip) {
+        const u32 k = (u32)(inits.size() / W);
+        skip.assign((k + 31) / 32, 0u);
+        u64 dups = 0;
+        std::set<std::vector<u64>> seen;
+        for (u32 i = 0; i < k; ++i)
+            if (!seen.insert(std::vector<u64>(&inits[(size_t)i * W], &inits[(size_t)i * W] + W)).second) {
+                const u32 at = k - 1 - i;  // init state i is arena index k - 1 - i
+                skip[at >> 5] |= 1u << (at & 31);
+                ++dups;
+            }
+        return dups;
+    }
+
     // The coverage pass (cover.hpp, kernels_cover.hpp) behind a search that explored everything: one launch
     // of cover_count over the arena, the persistent grid sized from the kernel's occupancy, and one read-back
     // of its 64-bit counters. Level 0 of the arena holds the init states as given, in REVERSE order: the
@@ -1511,17 +1556,8 @@ class Engine final : public EngineBase {
         const u64 n = lstart_.back();
         const std::vector<u64> inits = init_states_of(m_);
         const u32 k = (u32)(inits.size() / W);
-        std::vector<u32> skip((k + 31) / 32, 0u);
-        u64 dups = 0;
-        {
-            std::set<std::vector<u64>> seen;
-            for (u32 i = 0; i < k; ++i)
-                if (!seen.insert(std::vector<u64>(&inits[(size_t)i * W], &inits[(size_t)i * W] + W)).second) {
-                    const u32 at = k - 1 - i;  // init state i is arena index k - 1 - i
-                    skip[at >> 5] |= 1u << (at & 31);
-                    ++dups;
-                }
-        }
+        std::vector<u32> skip;
+        const u64 dups = repeated_inits(inits, skip);
         DBuf<u64> g;
         DBuf<u32> skip_d;
         const size_t words = cover_words(C);
@@ -1566,6 +1602,97 @@ class Engine final : public EngineBase {
             std::fprintf(stderr, "[sr] coverage: %llu states, %u classes, grid %llu x %u, %u strides per flush, %.3f ms\n",
                          (unsigned long long)f.c.states, C, (unsigned long long)grid, COVER_BLOCK, chunk, f.c.pass_ms);
         cover = std::move(f);
+    }
+
+    // The step pass (step.hpp, kernels_step.hpp) behind a search that explored everything: one launch of
+    // step_scan over the arena for all step properties of the model, the persistent grid sized from the kernel's
+    // occupancy, and one read-back of its 64-bit counters. Per property with a violation then: the level of its
+    // lowest violating arena index, W + 1 launches of step_min over that level, enqueued back to back, one more
+    // read-back, and the witness: the tree path to the seed's source and the seed's step, accepted on the host
+    // model (step_accept) before it becomes the discovery of p. Every buffer lives for this call only.
+    // SR_STEP_GRID (tests: several strides on a small arena) overrides the grid.
+    void step_pass() {
+        if constexpr (has_smask<M>::value && !is_canon<M>::value && !is_evbits<M>::value) {
+            const auto t0 = Clock::now();
+            const u64 n = lstart_.back();
+            const std::vector<u64> inits = init_states_of(m_);
+            const u32 k = (u32)(inits.size() / W);
+            std::vector<u32> skip;
+            const u64 dups = repeated_inits(inits, skip);
+            DBuf<u64> g;  // [the counters | the seed's W words | its slot | its arena index]
+            DBuf<u32> skip_d;
+            g.alloc(o_.device, STEP_WORDS + W + 2);
+            SR_HIP(hipMemsetAsync(g.p, 0, STEP_LOW * sizeof(u64), stream_));
+            SR_HIP(hipMemsetAsync(g.p + STEP_LOW, 0xff, (STEP_WORDS - STEP_LOW) * sizeof(u64), stream_));
+            if (dups) {
+                skip_d.alloc(o_.device, skip.size());
+                SR_HIP(hipMemcpyAsync(skip_d.p, skip.data(), skip.size() * sizeof(u32), hipMemcpyHostToDevice, stream_));
+            }
+            int per_cu = 0, cus = 0;
+            SR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)step_scan<M>, STEP_BLOCK, 0));
+            SR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o_.device));
+            u64 grid = per_cu > 0 && cus > 0 ? (u64)per_cu * (u64)cus : 1024;
+            if (const char* e = std::getenv("SR_STEP_GRID"))
+                if (std::atoi(e) > 0) grid = (u64)std::atoi(e);
+            grid = std::max<u64>(1, std::min<u64>(grid, (n + STEP_BLOCK - 1) / STEP_BLOCK));
+            step_scan<M><<<(u32)grid, STEP_BLOCK, 0, stream_>>>(m_, arena_.p, n, dups ? skip_d.p : nullptr, dups ? k : 0u, smask_, g.p);
+            SR_HIP(hipGetLastError());
+            std::vector<u64> h(STEP_WORDS);
+            SR_HIP(hipMemcpyAsync(h.data(), g.p, STEP_WORDS * sizeof(u64), hipMemcpyDeviceToHost, stream_));
+            SR_HIP(stream_sync(stream_));
+            const double scan_ms = secs(t0, Clock::now()) * 1e3;
+            step.assign(M::NPROPS, step_none());
+            for (int p = 0; p < M::NPROPS; ++p) {
+                if (!(smask_ >> p & 1)) continue;
+                const auto t1 = Clock::now();
+                sr_step_result& r = step[p];
+                r.ran = 1;
+                r.edges = h[0];
+                r.violations = h[STEP_VIOL + p];
+                r.sources = h[STEP_SRC + p];
+                r.scan_ms = scan_ms;
+                if (r.violations && !disc[p].found) {
+                    const u64 low = h[STEP_LOW + p];
+                    if (low >= n) throw Error(SR_ERR_HIP, "step pass: the scan counts violating edges and names no source");
+                    // the level of the lowest violating arena index is the lowest depth of a violating source
+                    const size_t level = (size_t)(std::upper_bound(lstart_.begin(), lstart_.end(), low) - lstart_.begin()) - 1;
+                    const u64 lo = lstart_[level], hi = lstart_[level + 1];
+                    u64* const seed_d = g.p + STEP_WORDS;
+                    SR_HIP(hipMemsetAsync(seed_d, 0xff, (W + 2) * sizeof(u64), stream_));
+                    for (int j = 0; j <= W; ++j)
+                        step_min<M><<<blocks_for(hi - lo, STEP_BLOCK), STEP_BLOCK, 0, stream_>>>(m_, arena_.p, lo, hi, p, j, seed_d);
+                    SR_HIP(hipGetLastError());
+                    u64 seed[W + 2];
+                    SR_HIP(hipMemcpyAsync(seed, seed_d, sizeof(seed), hipMemcpyDeviceToHost, stream_));
+                    SR_HIP(stream_sync(stream_));
+                    const u64 slot = seed[W], at = seed[W + 1];
+                    if (at < lo || at >= hi || slot >= (u64)64 * M::MW)
+                        throw Error(SR_ERR_HIP, "step pass: the tie-break found no seed in the level of the lowest violating source");
+                    std::vector<u64> path;
+                    tree_path((u32)level, (u32)(at - lo), path);
+                    if (path.size() != (level + 1) * W || !std::equal(seed, seed + W, path.end() - W))
+                        throw Error(SR_ERR_HIP, "step pass: the seed's tree path does not end at the seed's source");
+                    u64 out[W];
+                    if (!m_.apply(seed, (int)slot, out)) throw Error(SR_ERR_NONDETERMINISM, "step pass: the seed's slot yields no state on the host model");
+                    path.insert(path.end(), out, out + W);
+                    const std::vector<i64> acts = step_accept(m_, p, path, (int)slot);
+                    r.step_index = (int64_t)level;
+                    r.step_action = acts.back();
+                    r.witness_len = (int64_t)acts.size();
+                    r.init_index = step_init_index<M>(inits, path.data());
+                    if (r.init_index < 0) throw Error(SR_ERR_NONDETERMINISM, "step pass: the witness starts at no init state");
+                    live_path_[p] = path;
+                    step_action_[p] = r.step_action;
+                    disc[p].found = true;
+                    disc[p].level = disc[p].rank = 0;
+                }
+                r.min_ms = secs(t1, Clock::now()) * 1e3;
+                if (o_.verbose)
+                    std::fprintf(stderr, "[sr] step pass \"%s\": %llu edges, %llu violations, %llu sources, scan %.3f ms, seed %.3f ms\n",
+                                 m_.prop_name(p), (unsigned long long)r.edges, (unsigned long long)r.violations,
+                                 (unsigned long long)r.sources, r.scan_ms, r.min_ms);
+            }
+        }
     }
 
     // The complete `eventually` check (live.hpp, kernels_live.hpp) behind a search that explored
@@ -2242,7 +2369,8 @@ class Engine final : public EngineBase {
         sg.pass_ms = secs(f.t0, Clock::now()) * 1e3;
     }
 
-    std::vector<std::vector<u64>> live_path_;  // per property: the states of a discovery made by the liveness pass
+    std::vector<std::vector<u64>> live_path_;  // per property: the states of a discovery made by the liveness pass (or the step pass)
+    std::vector<i64> step_action_;             // per property: the last action of a step property's witness (-1: none)
 
     // Launch of the level whose frontier (n states) ends the arena, after the previous one is done:
     // the visited set and the arena are grown first if the level might not fit.
@@ -2551,6 +2679,7 @@ class Engine final : public EngineBase {
     u32 D_;  // max successors of one state (bounds the new states a chunk can create)
     u32 emask_;  // the model's `eventually` properties
     u32 lmask_;  // the model's leads-to properties (live.hpp LEADS-TO): never in a kernel's `undiscovered`
+    u32 smask_;  // the model's step properties (step.hpp): likewise
     bool fifo_ = false;
     int probe_batch_ = 0;  // SR_PROBE_BATCH: 1 forces the probe rounds, -4 the per-lane probe queues (0: probe_loop)
     // expand_fast's probe loop (DESIGN.md §3 "Probe loops"): rounds of one successor per lane, or

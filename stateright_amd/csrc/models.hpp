@@ -26,7 +26,7 @@ using i64 = int64_t;
 
 #define SR_HD __host__ __device__ __forceinline__
 
-enum Expect { ALWAYS = 0, EVENTUALLY = 1, SOMETIMES = 2, LEADS_TO = 3 };
+enum Expect { ALWAYS = 0, EVENTUALLY = 1, SOMETIMES = 2, LEADS_TO = 3, ALWAYS_STEP = 4 };
 
 // Mask of a model's `eventually` properties (0 for models without an `emask()` member).
 template <class M, class = void>
@@ -51,6 +51,20 @@ struct has_lmask<M, std::void_t<decltype(std::declval<const M&>().lmask())>> : s
 template <class M>
 inline u32 model_lmask(const M& m) {
     if constexpr (has_lmask<M>::value) return m.lmask();
+    else return 0;
+}
+
+// Mask of a model's STEP properties (0 for models without an `smask()` member). Such a property p
+// (`expectation(p) == ALWAYS_STEP`) is an invariant over steps, TLA+'s [][A]_v: `step_holds(p, s, a, t)` says
+// whether the step from s through slot a to t is allowed. `discovers(p, .)` is false everywhere, and its bit is
+// in no `undiscovered` mask handed to a kernel of the search: only the step pass decides it (step.hpp).
+template <class M, class = void>
+struct has_smask : std::false_type {};
+template <class M>
+struct has_smask<M, std::void_t<decltype(std::declval<const M&>().smask())>> : std::true_type {};
+template <class M>
+inline u32 model_smask(const M& m) {
+    if constexpr (has_smask<M>::value) return m.smask();
     else return 0;
 }
 
@@ -664,6 +678,29 @@ struct TwoPhaseLive : TwoPhase {
 };
 
 // -----------------------------------------------------------------------------------------------
+// TwoPhaseStep(n): two-phase commit with two STEP properties after its three (no reference counterpart;
+// the model of the step pass, step.hpp). State, slots, `apply` and every hook are TwoPhase's, so its counts
+// are 2pc's; the search never evaluates the two.
+//   3  step "a decided RM stays decided": an rm that is Committed or Aborted keeps its rm_state (holds: only
+//      RmRcvCommitMsg / RmRcvAbortMsg write a decided rm, and Commit and Abort are never both sent)
+//   4  step "the TM never aborts once an RM is prepared": refuted by RmPrepare(rm), TmAbort
+// -----------------------------------------------------------------------------------------------
+struct TwoPhaseStep : TwoPhase {
+    static constexpr int NPROPS = 5;
+    u32 smask() const { return 3u << 3; }
+    SR_HD bool discovers(int p, const u64* sp) const { return p < 3 && TwoPhase::discovers(p, sp); }
+    SR_HD bool step_holds(int p, const u64* sp, int a, const u64* tp) const {
+        const u64 ev = even_mask(), hi = (sp[0] >> 1) & ev, lo = sp[0] & ev;
+        if (p == 3) return ((sp[0] ^ tp[0]) & (hi | hi << 1)) == 0;
+        return !(a == 1 && (lo & ~hi) != 0);
+    }
+    int expectation(int p) const { return p < 3 ? TwoPhase::expectation(p) : ALWAYS_STEP; }
+    const char* prop_name(int p) const {
+        return p < 3 ? TwoPhase::prop_name(p) : p == 3 ? "a decided RM stays decided" : "the TM never aborts once an RM is prepared";
+    }
+};
+
+// -----------------------------------------------------------------------------------------------
 // Ladder(K, F): a test fixture (no reference counterpart) for models with `action_masks` whose slot
 // count passes 64, where a table held one slot per lane and a one-word mask both end. K rungs are
 // climbed in order and F free bits are set in any order: (K + 1) * 2^F states, depth K + F.
@@ -1081,6 +1118,30 @@ struct LeadsGraphT : LiveGraphT<W_> {
     const char* prop_name(int p) const { return p == 0 ? "marked" : p == 1 ? "armed ~> marked" : "always eventually marked"; }
 };
 using LeadsGraph = LeadsGraphT<1>;
+
+// -----------------------------------------------------------------------------------------------
+// StepGraph(n_bits, degree, seed, f_mod, t_mod, roots[, words[, dup]]): LiveGraph's graph, key and
+// description, with the two step properties of the step pass (step.hpp) and no other:
+//   0  "no forbidden step": the step (v, slot k) is forbidden iff f_mod > 0 and
+//      r(v, degree + 3 + k) % f_mod == 0 (f_mod up to 2^63 - 1: a large one forbids nothing);
+//   1  "never down": violated iff the successor is below v, so the hook has to read the successor.
+// -----------------------------------------------------------------------------------------------
+template <int W_>
+struct StepGraphT : LiveGraphT<W_> {
+    using B = LiveGraphT<W_>;
+    static constexpr int NPROPS = 2;
+    u64 f_mod = 0;
+    u32 emask() const { return 0u; }
+    u32 smask() const { return 3u; }
+    SR_HD bool discovers(int, const u64*) const { return false; }
+    SR_HD bool step_holds(int p, const u64* s, int a, const u64* t) const {
+        if (p == 0) return !(f_mod && B::r(s[0], (u64)B::degree + 3 + (u64)a) % f_mod == 0);
+        return !(t[0] < s[0]);
+    }
+    int expectation(int) const { return ALWAYS_STEP; }
+    const char* prop_name(int p) const { return p == 0 ? "no forbidden step" : "never down"; }
+};
+using StepGraph = StepGraphT<1>;
 
 // -----------------------------------------------------------------------------------------------
 // SpinLock(n): n threads take a lock in turn while a clock ticks (no reference counterpart; the

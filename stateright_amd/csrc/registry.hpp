@@ -60,6 +60,7 @@ std::unique_ptr<EngineBase> reg_fair_rings(const EngineArgs& a);      // FairRin
 std::unique_ptr<EngineBase> reg_leads(const EngineArgs& a);           // LeadsGraph (W = 1, 2, 4), LeadsDGraph
 std::unique_ptr<EngineBase> reg_req_lock(const EngineArgs& a);        // ReqLock, 1..4 threads
 std::unique_ptr<EngineBase> reg_req_lock_wide(const EngineArgs& a);   // ReqLock, 5..8 threads
+std::unique_ptr<EngineBase> reg_step(const EngineArgs& a);            // StepGraph (W = 1, 2, 4), StepDGraph, TwoPhaseStep
 
 // SpinLock (models.hpp) of (threads), handed to f: the engine (reg_spin_lock.hip) and the host-only entry
 // points (engine.hip) validate alike.
@@ -126,6 +127,30 @@ auto with_leads_graph(const i64* p, int np, F&& f) {
         m.q_mod = (u32)p[6];
         return f(m);
     });
+}
+
+// The StepGraph fixture (models.hpp) of (n_bits, degree, seed, f_mod, t_mod, roots) and optionally words and
+// dup: LiveGraph's parameters with f_mod (any non-negative int64) in p_mod's place, handed to f.
+template <class F>
+auto with_step_graph(const i64* p, int np, F&& f) {
+    if (np < 6 || np > 8) throw Error(SR_ERR_ARG, "step graph needs 6 params (n_bits, degree, seed, f_mod, t_mod, roots) and optionally words, dup");
+    if (p[3] < 0) throw Error(SR_ERR_ARG, "step graph: f_mod must not be negative");
+    i64 lp[8] = {p[0], p[1], p[2], 0, p[4], p[5], np > 6 ? p[6] : 1, np > 7 ? p[7] : 0};
+    return with_live_graph(lp, 8, [&](const auto& g) {
+        constexpr int GW = std::decay_t<decltype(g)>::W;
+        StepGraphT<GW> m;
+        static_cast<LiveGraphT<GW>&>(m) = g;
+        m.f_mod = (u64)p[3];
+        return f(m);
+    });
+}
+
+// TwoPhaseStep (models.hpp) of (rm_count), handed to f.
+template <class F>
+auto with_two_phase_step(const i64* p, int np, F&& f) {
+    if (np < 1) throw Error(SR_ERR_ARG, "2pc-step needs 1 param (rm_count)");
+    if (p[0] < 1 || p[0] > 14) throw Error(SR_ERR_UNSUPPORTED, "2pc-step: rm_count must be in 1..=14 (4n+4 <= 63 bits)");
+    return f(TwoPhaseStep{{(int)p[0], 0}});
 }
 
 // ReqLock (models.hpp) of (threads), handed to f as ReqLockT<threads>: the engines (reg_req_lock.hip for LO = 1,

@@ -338,6 +338,59 @@ class LeadsDGraph(_Model):
         return p
 
 
+class StepGraph(_Model):
+    """`LiveGraph`'s graph with two step properties and no other (csrc/models.hpp `StepGraph`; no reference
+    counterpart), the fixture of the step pass: 0 "no forbidden step", where the step (v, slot k) is forbidden
+    iff f_mod > 0 and r(v, degree + 3 + k) % f_mod == 0; 1 "never down", violated iff the successor is below v."""
+    MODEL_ID = N.SR_MODEL_STEP_GRAPH
+
+    def __init__(self, n_bits, degree, seed, f_mod, t_mod=0, roots=1, words=1, dup=0):
+        self.n_bits, self.degree, self.seed, self.f_mod, self.t_mod, self.roots = n_bits, degree, seed, f_mod, t_mod, roots
+        self.words, self.dup = words, dup
+
+    def params(self):
+        p = [self.n_bits, self.degree, self.seed, self.f_mod, self.t_mod, self.roots]
+        if self.dup:
+            return p + [self.words, self.dup]
+        return p if self.words == 1 else p + [self.words]
+
+
+class StepDGraph(_Model):
+    """`DGraph`'s adjacency from paths with an explicit list of forbidden (src, dst) pairs, at most 16
+    (csrc/dgraph.hpp `StepDGraph`), for hand-drawn graphs of at most 256 states: one step property "no forbidden
+    step". A pair that is no edge of the graph forbids nothing."""
+    MODEL_ID = N.SR_MODEL_STEP_DGRAPH
+
+    def __init__(self, forbidden=(), paths=()):
+        self.forbidden = [tuple(f) for f in forbidden]
+        self.paths = [list(p) for p in paths]
+
+    def with_path(self, path):
+        return StepDGraph(self.forbidden, self.paths + [list(path)])
+
+    def params(self):
+        p = [len(self.forbidden)]
+        for src, dst in self.forbidden:
+            p.extend((src, dst))
+        for path in self.paths:
+            p.append(len(path))
+            p.extend(path)
+        return p
+
+
+class TwoPhaseStepSys(_Model):
+    """`TwoPhaseSys` with two step properties after its three (csrc/models.hpp `TwoPhaseStep`; no reference
+    counterpart): "a decided RM stays decided" (holds) and "the TM never aborts once an RM is prepared" (refuted
+    by RmPrepare, TmAbort). States, actions and counts are 2pc's; only the step pass decides the two."""
+    MODEL_ID = N.SR_MODEL_2PC_STEP
+
+    def __init__(self, rm_count):
+        self.rm_count = rm_count
+
+    def params(self):
+        return [self.rm_count]
+
+
 class SingleCopyRegister(_Model):
     """The single-copy register `SingleCopyModelCfg { client_count, server_count }.into_model()`
     (examples/single-copy-register.rs:40-78): SingleCopyActor servers (a register value each, no
