@@ -214,6 +214,12 @@ typedef struct sr_opts {
                                     sr_gpu_bfs_coverage below); 0 = off, and then nothing changes. What was
                                     `reserved1`: the size and every offset are unchanged, and a caller
                                     whose struct_size is 56 is read as coverage = 0                  */
+    int32_t certify;             /* 1 = the certificate pass behind a one-GPU check (see sr_gpu_bfs_certificate
+                                    below); 0 = off, and then nothing changes. The search launches the
+                                    kernels it launches without it; the visited set is only kept until the
+                                    pass has run. The struct grew from 64 to 72 bytes for it: a caller
+                                    whose struct_size is 64 is read as certify = 0                   */
+    int32_t reserved1;           /* tail padding made explicit; never read                           */
 } sr_opts;
 
 /* Timing/throughput counters of a finished run (sr_gpu_bfs_stats / sr_gpu_bfs_stats_sized).
@@ -1009,6 +1015,58 @@ int32_t sr_gpu_bfs_table_audit(const sr_bfs* bfs, sr_table_audit* out, uint32_t 
  * device < 0: host only, nothing is launched: every case is built and its expectations checked
  * against the host model (the random fill must spill, the long run must extend its window twice). */
 int32_t sr_selftest_rehash_gpu(int32_t device);
+
+/* ---- The certificate of a finished check (sr_opts.certify; stateright_amd/csrc/certify.hpp has the exact
+ * definitions) ----
+ * After the search, GPU passes re-derive from the arena, its level offsets, the parent ranks and the final
+ * visited set that the arena lists exactly the reachable set, level by level, with a valid BFS tree, and in
+ * FIFO order in the reference's visit order. A clean certificate has every error counter at 0. One GPU only:
+ * a partitioned check leaves ran = 0. The closure counters are filled only when the search explored everything
+ * (explored_all); after an early exit or a target stop the roots, map, tree, order and property figures hold.
+ * The first `inits` arena states are the init states in REVERSE order, as the reference visits them. */
+typedef struct sr_certificate {
+    uint32_t ran;              /* 1: the pass ran; else every counter is 0                                    */
+    uint32_t fifo;             /* 1: FIFO order, the tags (meta) were checked                                 */
+    uint32_t explored_all;     /* 1: the search explored everything, the closure pass ran                     */
+    uint32_t skipped;          /* 1: the level map (4 bytes per slot) could not be allocated; ran = 0         */
+    uint64_t states;           /* arena states (every level the check accounted for)                          */
+    uint64_t levels;           /* arena levels                                                                */
+    uint64_t inits;            /* init states, as the model lists them                                        */
+    uint64_t repeated_inits;   /* ... that repeat an earlier one                                              */
+    uint64_t roots_wrong;      /* level 0: indices that do not hold their init state                          */
+    uint64_t map_missing;      /* states the table does not hold                                              */
+    uint64_t tree_range;       /* parent ranks at or past the previous level's size (counted, never loaded)   */
+    uint64_t tree_edge;        /* states that no enabled slot of their parent produces                        */
+    uint64_t tree_slot;        /* FIFO: states whose tag is not parent rank * max_actions + first such slot   */
+    uint64_t edges;            /* (state, enabled slot) pairs whose apply succeeds, repeated init states aside */
+    uint64_t repeated_edges;   /* ... of the repeated init states: inits + edges + repeated_edges is the
+                                  search's state_count                                                        */
+    uint64_t closure_missing;  /* successors the table does not hold                                          */
+    uint64_t closure_unlisted; /* successors in a slot that no arena state maps to                            */
+    uint64_t closure_late;     /* successors listed more than one level below their generator                 */
+    uint64_t fifo_not_first;   /* FIFO: successors one level down with an earlier generator than the recorded */
+    uint64_t fifo_order;       /* FIFO: neighbours of a level whose tags do not strictly increase             */
+    uint32_t nprops;           /* the model's properties                                                      */
+    uint32_t pmask;            /* the ones counted below: those outside emask() | lmask() | smask()           */
+    uint64_t holds[32];        /* per property: states where `discovers` holds                                */
+    uint64_t first_index[32];  /* ... the lowest such arena index (all ones: none)                            */
+    uint64_t disc_index[32];   /* ... the engine's own discovery, lstart[level] + rank (all ones: none)       */
+    uint64_t disc_wrong[32];   /* ... 1: `discovers` is false there                                           */
+    uint32_t first_level[32];  /* ... the level of first_index (all ones: none)                               */
+    uint32_t disc_level[32];   /* ... the level of disc_index (all ones: none, or past the arena)             */
+    double pass_ms;            /* host time of the pass                                                       */
+} sr_certificate;
+/* Copies at most `size` bytes of the finished check's certificate; returns the engine's
+ * sizeof(sr_certificate), or SR_ERR_ARG. */
+int32_t sr_gpu_bfs_certificate(const sr_bfs* bfs, sr_certificate* out, uint32_t size);
+/* Self-test of the certificate kernels (csrc/certify_selftest.hpp): arenas and tables built on the host by a
+ * sequential search of small models, clean and with planted errors (a wrong parent, an out-of-range parent
+ * rank, a missing or unowned table entry, a late or unreachable state, swapped neighbours, a later generator's
+ * tag, a replaced init state); every counter of every case must equal the host evaluation of the definitions.
+ * SR_OK, or SR_ERR_ARG with the first failing case in sr_last_error (SR_ERR_HIP: a runtime error).
+ * device < 0: host only, nothing is launched: the cases are built, evaluated and cross-checked (a clean arena
+ * gives zeros, every planted error moves the counter it was planted for). */
+int32_t sr_selftest_certify_gpu(int32_t device);
 
 #ifdef __cplusplus
 }

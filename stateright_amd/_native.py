@@ -56,6 +56,8 @@ class sr_opts(ctypes.Structure):
         ("reserved0", ctypes.c_int32),
         ("liveness", ctypes.c_int32),  # (the struct grew from 56 to 64 bytes for it)
         ("coverage", ctypes.c_int32),  # (what was reserved1: same offset)
+        ("certify", ctypes.c_int32),  # (the struct grew from 64 to 72 bytes for it)
+        ("reserved1", ctypes.c_int32),
     ]
 
 
@@ -266,6 +268,51 @@ class sr_table_audit(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class sr_certificate(ctypes.Structure):
+    _fields_ = [
+        ("ran", ctypes.c_uint32),
+        ("fifo", ctypes.c_uint32),
+        ("explored_all", ctypes.c_uint32),
+        ("skipped", ctypes.c_uint32),
+        ("states", ctypes.c_uint64),
+        ("levels", ctypes.c_uint64),
+        ("inits", ctypes.c_uint64),
+        ("repeated_inits", ctypes.c_uint64),
+        ("roots_wrong", ctypes.c_uint64),
+        ("map_missing", ctypes.c_uint64),
+        ("tree_range", ctypes.c_uint64),
+        ("tree_edge", ctypes.c_uint64),
+        ("tree_slot", ctypes.c_uint64),
+        ("edges", ctypes.c_uint64),
+        ("repeated_edges", ctypes.c_uint64),
+        ("closure_missing", ctypes.c_uint64),
+        ("closure_unlisted", ctypes.c_uint64),
+        ("closure_late", ctypes.c_uint64),
+        ("fifo_not_first", ctypes.c_uint64),
+        ("fifo_order", ctypes.c_uint64),
+        ("nprops", ctypes.c_uint32),
+        ("pmask", ctypes.c_uint32),
+        ("holds", ctypes.c_uint64 * 32),
+        ("first_index", ctypes.c_uint64 * 32),
+        ("disc_index", ctypes.c_uint64 * 32),
+        ("disc_wrong", ctypes.c_uint64 * 32),
+        ("first_level", ctypes.c_uint32 * 32),
+        ("disc_level", ctypes.c_uint32 * 32),
+        ("pass_ms", ctypes.c_double),
+    ]
+
+    # the error counters: all 0 in a clean certificate (the per-property disc_wrong aside)
+    ERRORS = ("roots_wrong", "map_missing", "tree_range", "tree_edge", "tree_slot", "closure_missing", "closure_unlisted",
+              "closure_late", "fifo_not_first", "fifo_order")
+
+    def as_dict(self):
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = list(v)[:self.nprops] if name in ("holds", "first_index", "disc_index", "disc_wrong", "first_level", "disc_level") else v
+        return out
+
+
 class sr_dist_host_opts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
@@ -424,6 +471,8 @@ SIGNATURES = [
                                           ctypes.POINTER(sr_opts)]),
     ("sr_gpu_bfs_table_audit", ctypes.c_int32, [_P, ctypes.POINTER(sr_table_audit), ctypes.c_uint32]),
     ("sr_selftest_rehash_gpu", ctypes.c_int32, [ctypes.c_int32]),
+    ("sr_gpu_bfs_certificate", ctypes.c_int32, [_P, ctypes.POINTER(sr_certificate), ctypes.c_uint32]),
+    ("sr_selftest_certify_gpu", ctypes.c_int32, [ctypes.c_int32]),
 ]
 
 SR_DIST_ID_BYTES = 128

@@ -20,7 +20,7 @@ UNITS = ["engine.hip", "reg_basic.hip", "reg_two_phase.hip", "reg_increment.hip"
          "reg_req_lock.hip", "reg_req_lock_wide.hip", "reg_step.hip"]
 CSRC = [os.path.join(CDIR, f) for f in UNITS + ["registry.hpp", "engine.hpp", "kernels.hpp", "kernels_dist.hpp",
                                                 "dist.hpp", "dist_host.hpp", "sim.hpp", "kernels_sim.hpp", "live.hpp", "kernels_live.hpp", "cover.hpp", "kernels_cover.hpp", "step.hpp", "kernels_step.hpp", "models.hpp", "device.hpp", "paxos.hpp", "dgraph.hpp",
-                                                "actor.hpp", "abd_wide.hpp", "table_selftest.hpp", "kernels_audit.hpp", "rehash_selftest.hpp"]]
+                                                "actor.hpp", "abd_wide.hpp", "table_selftest.hpp", "kernels_audit.hpp", "rehash_selftest.hpp", "certify.hpp", "kernels_certify.hpp", "certify_selftest.hpp"]]
 HEADERS = [os.path.join(ROOT, "include", f) for f in ("stateright_gpu.h", "stateright_gpu_model.hpp")]
 OUT = os.path.join(HERE, "libstateright_gpu.so")
 OBJDIR = os.path.join(HERE, "build")

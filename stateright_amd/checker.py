@@ -258,6 +258,17 @@ class CheckerBuilder:
         self._opts.liveness = N.SR_LIVENESS_STRONG if on else 0
         return self
 
+    def certify(self, on=True):
+        """Engine opt-in: the certificate pass. Behind a `spawn_bfs` / `spawn_dfs` on one
+        GPU, kernels that share nothing with the search but the model and the table's lookup re-derive from
+        the arena, the parent ranks and the final visited set that the arena starts with the init states, that
+        every state has a parent in the level before it that produces it, that the arena is closed under
+        successors with none listed late, and in FIFO order that the visit order is the reference's:
+        `GpuBfsChecker.certificate()`. The search launches what it launches without the option. A
+        partitioned spawn leaves the certificate's `ran` at 0."""
+        self._opts.certify = int(bool(on))
+        return self
+
     def coverage(self, on=True):
         """Engine opt-in: the coverage pass. A `spawn_bfs` / `spawn_dfs` on one GPU
         that explored everything is followed by one more expansion of every reachable state on the GPU,
@@ -616,6 +627,21 @@ class GpuBfsChecker:
         if st < 0:
             raise CheckerError("sr_gpu_bfs_table_audit", st)
         return a.as_dict()
+
+    def certificate(self):
+        """The certificate pass' figures (`CheckerBuilder.certify()`; joins the check), a dict of sr_certificate:
+        ran, fifo, explored_all, skipped, states, levels, inits, repeated_inits, the error counters roots_wrong,
+        map_missing, tree_range, tree_edge, tree_slot, closure_missing, closure_unlisted, closure_late,
+        fifo_not_first and fifo_order (all 0 when clean), edges and repeated_edges (inits + edges +
+        repeated_edges == state_count() when explored_all), pmask, and per property (lists in property order)
+        holds, first_index, disc_index, disc_wrong, first_level and disc_level; all ones (2^64 - 1) stands for "none". ran is 0 without
+        the option, and after a partitioned spawn."""
+        self.join()
+        c = N.sr_certificate()
+        st = self._lib.sr_gpu_bfs_certificate(self._h, ctypes.byref(c), ctypes.sizeof(c))
+        if st < 0:
+            raise CheckerError("sr_gpu_bfs_certificate", st)
+        return c.as_dict()
 
     def liveness(self, name):
         """The complete `eventually` check's outcome for property `name` (`complete_liveness()`), a dict:

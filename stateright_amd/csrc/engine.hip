@@ -8,6 +8,7 @@
 #include "dist_host.hpp"
 #include "table_selftest.hpp"
 #include "rehash_selftest.hpp"
+#include "certify_selftest.hpp"
 
 namespace sr {
 
@@ -1509,6 +1510,29 @@ int32_t sr_selftest_rehash_gpu(int32_t device) {
         set_error(x.what());
         return SR_ERR_ARG;
     }
+}
+
+int32_t sr_selftest_certify_gpu(int32_t device) {
+    try {
+        std::string why;
+        if (!cert_test::run_all(device, why, device < 0)) {
+            set_error(why);
+            return SR_ERR_ARG;
+        }
+        return SR_OK;
+    } catch (const Error& x) {
+        set_error(x.what());
+        return x.code;
+    } catch (const std::exception& x) {
+        set_error(x.what());
+        return SR_ERR_ARG;
+    }
+}
+
+int32_t sr_gpu_bfs_certificate(const sr_bfs* b, sr_certificate* out, uint32_t size) {
+    if (!b || (!out && size) || !b->e->finished.load(std::memory_order_acquire)) return SR_ERR_ARG;
+    if (out) std::memcpy(out, &b->e->cert, std::min<size_t>(size, sizeof(sr_certificate)));
+    return (int32_t)sizeof(sr_certificate);
 }
 
 int32_t sr_gpu_bfs_table_audit(const sr_bfs* b, sr_table_audit* out, uint32_t size) {

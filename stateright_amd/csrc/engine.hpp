@@ -28,6 +28,7 @@
 #include "live.hpp"
 #include "cover.hpp"
 #include "step.hpp"
+#include "certify.hpp"
 
 namespace sr {
 
@@ -146,6 +147,7 @@ class EngineBase {
     std::string error;
     sr_stats stats{};
     sr_table_audit audit{};  // the visited-set audit of a counting run (kernels_audit.hpp); ran = 0 otherwise
+    sr_certificate cert = cert_none();  // the certificate pass' figures (certify.hpp; ran = 0: it did not run)
     std::vector<DiscoveryRec> disc;
     std::vector<double> launch_ms;    // per timed launch (profile=1), in launch order
     std::vector<u64> launch_frontier; // the frontier each launch expanded (0 if unknown)
@@ -1092,6 +1094,7 @@ class Engine final : public EngineBase {
         stats.order_used = (u32)order;
         stats.restarts = restarts_;
         audit = sr_table_audit{};
+        cert = cert_none();
         launch_ms.clear();
         launch_frontier.clear();
         launch_probes.clear();
@@ -1322,6 +1325,7 @@ class Engine final : public EngineBase {
         collect_timing();
         displacement_stats();
         table_audit();
+        if (o_.certify) certify_pass(explored_all || cover_all);  // (reads the visited set: before its release)
         stats.level_loop_sec = secs(t_loop, t_end);
         stats.total_sec = secs(t_start, t_end);
         stats.table_capacity = cap_;
@@ -1488,11 +1492,12 @@ class Engine final : public EngineBase {
         // A speculative level past the end may still be in flight: the host waits for it, but the
         // visited set's clear for the next check is enqueued behind it first (release_table), so
         // that the clear runs while this check returns and the next one is set up.
+        // (the certificate pass reads the visited set after this loop: run_order releases it then)
         SR_HIP(hipEventRecord(ctx_->done, stream_));
-        release_table();
+        if (!o_.certify) release_table();
         drain(ctx_->done);
         check_async_growth();
-        free_unzeroed_table();
+        if (!o_.certify) free_unzeroed_table();
         return order_dependent;
     }
 
@@ -1602,6 +1607,30 @@ class Engine final : public EngineBase {
             std::fprintf(stderr, "[sr] coverage: %llu states, %u classes, grid %llu x %u, %u strides per flush, %.3f ms\n",
                          (unsigned long long)f.c.states, C, (unsigned long long)grid, COVER_BLOCK, chunk, f.c.pass_ms);
         cover = std::move(f);
+    }
+
+    // The certificate pass (certify.hpp, kernels_certify.hpp) behind any one-GPU search: the arena, its level
+    // offsets, the parent ranks and the final visited set, re-derived by kernels that share nothing with the
+    // search but the model and the table's lookup. all: the search explored everything (the closure pass runs).
+    // The option changes no launch of the search; it keeps the visited set until here. SR_CERT_GRID (tests:
+    // several strides on a small arena) overrides the persistent grids.
+    void certify_pass(bool all) {
+        if (!cap_ || !keys_.p) return;
+        SR_HIP(stream_sync(stream_));
+        CertInput in;
+        in.lstart = lstart_;
+        in.fifo = fifo_;
+        in.explored_all = all;
+        in.pmask = ((1u << M::NPROPS) - 1) & ~(emask_ | lmask_ | smask_);
+        for (int p = 0; p < M::NPROPS && p < 32; ++p)
+            if ((in.pmask >> p & 1) && disc[p].found && live_path_[p].empty() && disc[p].level + 1 < lstart_.size())
+                in.disc_index[p] = lstart_[disc[p].level] + disc[p].rank;
+        if (const char* e = std::getenv("SR_CERT_GRID"))
+            if (std::atoi(e) > 0) in.grid = (u32)std::atoi(e);
+        cert = cert_device(m_, view(), cap_, arena_.p, apar_.p, in, o_.device, stream_);
+        if (o_.verbose)
+            std::fprintf(stderr, "[sr] certificate: %llu states, %llu levels, %llu edges, ran %u, %.3f ms\n", (unsigned long long)cert.states,
+                         (unsigned long long)cert.levels, (unsigned long long)cert.edges, cert.ran, cert.pass_ms);
     }
 
     // The step pass (step.hpp, kernels_step.hpp) behind a search that explored everything: one launch of

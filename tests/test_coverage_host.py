@@ -188,11 +188,11 @@ def test_duplicate_init_states_count_once():
 
 
 def test_struct_sizes():
-    assert ctypes.sizeof(N.sr_opts) == 64 and N.sr_opts.coverage.offset == 60
+    assert ctypes.sizeof(N.sr_opts) == 72 and N.sr_opts.coverage.offset == 60
     assert ctypes.sizeof(N.sr_coverage) == 568 and N.sr_coverage.out_degree.offset == 56
     o = N.sr_opts()
     N.load().sr_opts_init(ctypes.byref(o))
-    assert o.struct_size == 64 and o.coverage == 0
+    assert o.struct_size == 72 and o.coverage == 0
 
 
 def _call(model_id, params, max_states, size=None):

@@ -150,7 +150,7 @@ def test_live_graph_describes_and_fingerprints():
 def test_opts_grew_for_the_option():
     # the old 56-byte struct ended in 4 bytes of padding: `liveness` lies beyond them, so that a caller's
     # struct_size of 56 says that it has none (tests/test_gpu_liveness.py spawns with such a struct)
-    assert N.ctypes.sizeof(N.sr_opts) == 64 and N.sr_opts.reserved0.offset == 52 and N.sr_opts.liveness.offset == 56
+    assert N.ctypes.sizeof(N.sr_opts) == 72 and N.sr_opts.reserved0.offset == 52 and N.sr_opts.liveness.offset == 56
     o = N.sr_opts()
     o.liveness = 7
     N.load().sr_opts_init_sized(N.ctypes.byref(o), 56)

@@ -278,7 +278,7 @@ def test_the_struct_and_the_mode_value():
                        "fair_states": 40, "stem_len": 48, "loop_len": 56, "scc_rounds": 64, "reach_rounds": 68, "segments": 72,
                        "reserved1": 76, "pass_ms": 80}
     assert ctypes.sizeof(N.sr_live_weak) == 88  # unchanged
-    assert ctypes.sizeof(N.sr_live_result) == 64 and ctypes.sizeof(N.sr_opts) == 64
+    assert ctypes.sizeof(N.sr_live_result) == 64 and ctypes.sizeof(N.sr_opts) == 72
 
 
 def test_the_builder_sets_and_clears_the_mode():

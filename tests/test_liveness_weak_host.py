@@ -228,7 +228,7 @@ def test_the_struct_and_the_mode_value():
     import ctypes
     assert N.SR_LIVENESS_WEAK == 3 and N.SR_MODEL_SPIN_LOCK == 17
     assert ctypes.sizeof(N.sr_live_weak) == 88
-    assert ctypes.sizeof(N.sr_live_result) == 64 and ctypes.sizeof(N.sr_opts) == 64  # unchanged
+    assert ctypes.sizeof(N.sr_live_result) == 64 and ctypes.sizeof(N.sr_opts) == 72  # (64 + the certificate pass' option)
 
 
 def test_the_builder_sets_and_clears_the_mode():
